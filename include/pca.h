@@ -226,6 +226,10 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts /*dev*/, int32_t n_src, 
  *       bev_generator/bev_generator.py:373-480 (counts, dirichlet, intensity), sem_bev.py:593-617, :204-257 (fp16).
  *     Output (dev): planes f64 [21,px,px] and/or planes_f16 [21,px,px] (either may be NULL), order
  *       set-major {present,future,full} x {road,intensity,r,g,b,dynamic,elevation}.
+ *     Grid: 1 <= px <= 4096 (else "bev: px must be in 1..4096").  Up to 1024 the grid is one piece; above, it runs as bands
+ *       of whole 8-cell tile rows of at most 16 384 tiles each (2048: 4 bands, 4096: 16), one pass over the window and one
+ *       launch of the tile kernels per band, all in the caller's planes -- same results as any other banding.  A banded call
+ *       takes no deferred K1 along (pca_k1_defer: it runs on its own first).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
     double origin[3];         /* bev_frame_coords                                                   */
@@ -236,14 +240,14 @@ typedef struct {
     double height_filter;     /* keep z < height_filter; NaN disables                               */
     double int_scaler, int_sep_scaler, int_mid_threshold;
     double rgb_fill;          /* value of an empty cell before /255                                 */
-    int32_t px;
+    int32_t px;               /* grid side [cells], 1..4096 (> 1024: banded, see above)         */
     int32_t road_class;
     uint64_t dynobj_mask[4];  /* classes counted in the 'dynamic' plane                             */
     int32_t intensity_div255;
     int32_t pad;
 } pca_bev_params;
 
-/* bytes of scratch the rasteriser needs for a window of at most max_points and a px x px grid */
+/* bytes of scratch the rasteriser needs for a window of at most max_points and a px x px grid (px > 1024: the bands share it) */
 int64_t pca_bev_workspace_bytes(int64_t max_points, int px);
 
 /* intensity64 (dev, may be NULL): f64 intensities indexed like the store, overriding store.intensity

@@ -103,6 +103,8 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
     double *extra;        // [3 sets][PCA_BEV_EXTRA_PLANES][px][px] or NULL
     uint32_t *status;     // context status word (PCA_STATUS_* bits)
     int dbg;
+    int band_r0, band_rows;   // banded rasters (px > 1024, the bev_*_band kernels): the band's first tile row and its tile rows;
+                          // T = band_rows * tx tiles, numbered from the band's first row.  Unused by the whole-grid kernels.
 };
 #define HQ_CLASSES 32
 #define HQ_CURSOR 32
@@ -231,7 +233,9 @@ __device__ __forceinline__ uint32_t view_key(const BevArgs &a, const Window &w, 
 }
 // One point of pass A (memory path): owed re-transform (returns the stored coordinates), BEV-frame key.
 struct ViewConst;
+template <bool BAND = false>
 __device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, double Y, double Z, bool live, uint32_t set);
+template <bool BAND>
 __device__ __forceinline__ BinPoint bin_point(const BevArgs &a, const ViewConst &vc, const Window &w, const PendHi &pend_hi, int64_t p,
                                               double X, double Y, double Z, uint8_t D)
 {
@@ -239,7 +243,7 @@ __device__ __forceinline__ BinPoint bin_point(const BevArgs &a, const ViewConst 
     const bool moved = apply_owed(a, pend_hi, p, X, Y, Z);
     if (moved && a.write_back) { a.st.x[p] = X; a.st.y[p] = Y; a.st.z[p] = Z; }
     r.x = X; r.y = Y; r.z = Z;
-    r.key = view_key_lean(vc, X, Y, Z, D != 1, p >= w.sp ? 1u : 0u);
+    r.key = view_key_lean<BAND>(vc, X, Y, Z, D != 1, p >= w.sp ? 1u : 0u);
     return r;
 }
 // packs and stores one kept record (pass B).  dynbits: the 256-bit set of 'dynamic object' classes as eight dwords in LDS
@@ -274,7 +278,7 @@ __device__ __forceinline__ void bin_store(const BevArgs &a, const uint32_t *dynb
 // as view_key: R is a rotation about z (checked by the host), so R[2] z, R[5] z, R[6] x and R[7] y are exact zeros and
 // R[8] z is z -- for FINITE z; a point whose z is not finite is dropped here, as the reference drops it (0 * inf = NaN
 // poisons its x and y).
-struct ViewConst { double ox, oy, oz, r0, r1, r3, r4, dx, dy, vlo, vhi, v, rv, pxd, half_px, hf; int px, tx; bool use_h; };
+struct ViewConst { double ox, oy, oz, r0, r1, r3, r4, dx, dy, vlo, vhi, v, rv, pxd, half_px, hf; int px, tx; bool use_h; uint32_t br0, brows; };
 __device__ __forceinline__ ViewConst view_const(const BevArgs &a)
 {
     const pca_bev_params &q = a.prm;
@@ -286,8 +290,12 @@ __device__ __forceinline__ ViewConst view_const(const BevArgs &a)
     // (handing 1 / view, (double)px and px / 2 over from the host instead was measured: 57.7-57.8 us against 56.8-57.2)
     c.hf = q.height_filter; c.use_h = !(q.height_filter != q.height_filter);
     c.px = q.px; c.tx = a.tx;
+    c.br0 = (uint32_t)a.band_r0; c.brows = (uint32_t)a.band_rows;   // (read by the BAND variant only)
     return c;
 }
+// BAND (banded rasters, px > 1024): i, j, the clamp and the row are those of the FULL grid; a point whose tile row lies outside
+// the band [br0, br0 + brows) gets KEY_INVALID, the others the key of their tile numbered within the band.
+template <bool BAND>
 __device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, double Y, double Z, bool live, uint32_t set)
 {
     const double x = X - c.ox, y = Y - c.oy;
@@ -300,7 +308,8 @@ __device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, 
         // floor(a / view * px + px / 2), the reference's expression.  The IEEE division (~22 instructions) is replaced by
         // the quotient estimate  q = a rv,  q += fma(-q, view, a) rv  (within one ulp of the rounded quotient): the floor
         // can only differ if the sum lands within a few ulps of an integer, and a sum within 1e-9 of one is recomputed
-        // with the real division (about two points in a billion).
+        // with the real division (about two points in a billion).  The margin holds up to the largest grid, px = 4096: |q| < 1/2,
+        // so ulp(q) px <= 2^-53 * 4096 ~ 4.5e-13, far below 1e-9.
         const double qx0 = ax * c.rv, qy0 = ay * c.rv;
         const double qx = fma(fma(-qx0, c.v, ax), c.rv, qx0), qy = fma(fma(-qy0, c.v, ay), c.rv, qy0);
         double tx = qx * c.pxd + c.half_px, ty = qy * c.pxd + c.half_px;
@@ -314,8 +323,9 @@ __device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, 
         i = i > c.px - 1 ? c.px - 1 : (i < 0 ? 0 : i);
         j = j > c.px - 1 ? c.px - 1 : (j < 0 ? 0 : j);
         const uint32_t row = (uint32_t)(c.px - 1 - j), col = (uint32_t)i;
-        const uint32_t tile = (row / TS) * (uint32_t)c.tx + (col / TS);
-        key = (tile << 7) | ((((row % TS) * TS + (col % TS)) * 2u) + set);
+        const uint32_t trow = BAND ? row / TS - c.br0 : row / TS;   // (BAND: wraps to a large number above the band)
+        const uint32_t tile = trow * (uint32_t)c.tx + (col / TS);
+        if (!BAND || trow < c.brows) key = (tile << 7) | ((((row % TS) * TS + (col % TS)) * 2u) + set);
     }
     return key;
 }
@@ -367,7 +377,7 @@ __device__ __forceinline__ void bin_scan_tables(const BevArgs &a, const uint32_t
 }
 }
 
-template <bool I64>
+template <bool I64, bool BAND = false>
 __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
 {
     constexpr int REG_P = I64 ? 0 : BIN_REG_P;
@@ -491,7 +501,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x;
-                rkey[j0 + u] = view_key_lean(vc, X[u], Y[u], Z[u], i < n_reg && D[u] != 1u, i >= sp_rel ? 1u : 0u);
+                rkey[j0 + u] = view_key_lean<BAND>(vc, X[u], Y[u], Z[u], i < n_reg && D[u] != 1u, i >= sp_rel ? 1u : 0u);
                 rz[j0 + u] = Z[u];
                 if (rkey[j0 + u] != KEY_INVALID) atomicAdd(&s_h[rkey[j0 + u] >> hs], 1u);
             }
@@ -525,7 +535,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
         for (int u = 0; u < MUNR; ++u) {
             const int64_t p = base + u * AB_THREADS;
             if (p >= w.c_hi) continue;
-            const BinPoint b = bin_point(a, vcm, w, pend_hi, p, X[u], Y[u], Z[u], D[u]);
+            const BinPoint b = bin_point<BAND>(a, vcm, w, pend_hi, p, X[u], Y[u], Z[u], D[u]);
             if (b.key != KEY_INVALID) atomicAdd(&s_h[b.key >> hs], 1u);
             a.key[p - w.lo] = b.key;
         }
@@ -894,6 +904,7 @@ __device__ __forceinline__ void load_rec_key_colour(const BevArgs &a, uint32_t r
 }
 
 // closed-form maps of the tile (thread -> (set, cell)), staged in LDS, then written row by row
+template <bool BAND = false>
 __device__ __forceinline__ void tile_finalize_write(const BevArgs &a, const TileStats &S, double (*s_out)[TCELLS], int tile,
                                                     int nthreads, int cell_lo = 0, int cell_hi = TCELLS)
 {
@@ -931,7 +942,7 @@ __device__ __forceinline__ void tile_finalize_write(const BevArgs &a, const Tile
         }
     }
     __syncthreads();
-    const int row0 = (tile / a.tx) * TS, col0 = (tile % a.tx) * TS;
+    const int row0 = (tile / a.tx + (BAND ? a.band_r0 : 0)) * TS, col0 = (tile % a.tx) * TS;   // (BAND: tiles count from the band's first row)
     const int64_t ncell = (int64_t)q.px * q.px;
     const int n_planes = extra ? 21 + PCA_BEV_EXTRA_PLANES * 3 : 21;
     // fp16 planes only, whole tile inside the grid: one 16-byte store per (plane, row of the tile) instead of eight 2-byte ones
@@ -1142,7 +1153,7 @@ __device__ __forceinline__ void tile_cell_medians32(TileStats &S, uint32_t (*his
 // every step on uniform data).  Should tiles be queued nonetheless -- the first dense tile of a sequence -- the LAST
 // workgroup of the light kernel to finish works them off, slowly but exactly: statistics in one pass, then 32-bit
 // histograms cell by cell.  It also tells the host, so that the next call launches the heavy kernel.
-template <bool I64>
+template <bool I64, bool BAND = false>
 __device__ __forceinline__ void cells_drain(const BevArgs &a, TileLds &L, unsigned char *s_buf, bool pushed)
 {
     TileStats &S = L.S;
@@ -1220,13 +1231,13 @@ __device__ __forceinline__ void cells_drain(const BevArgs &a, TileLds &L, unsign
                         tile_cell_medians32<I64, C_THREADS>(S, hist, M, a, cell, 0u, r_hi);
             }
             __syncthreads();
-            tile_finalize_write(a, S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
+            tile_finalize_write<BAND>(a, S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
         }
     }
 }
 
 #define DBG_STAMP(bit, slot) do { if ((a.dbg & (bit)) && threadIdx.x == 0 && tile < 1024) g_dbg_stamps[tile][slot] = wall_clock64(); } while (0)
-template <bool I64>
+template <bool I64, bool BAND = false>
 __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
 {
     __shared__ TileLds L;
@@ -1241,8 +1252,9 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     // tiles of one column (the CU totals then ranged 3 800..8 400 records, the kernel's span 30 us against a mean tile life of
     // 23).  Inside a band, workgroup i takes place i * tile_mult mod T/4 (tile_mult coprime to T/4), which interleaves dense
     // and empty tiles in dispatch order.  Grids whose tile count per side is not a multiple of four: one permutation of all.
+    // So are the bands of a banded raster (BAND: not square).
     int tile;
-    if ((a.tx & 3) == 0) {
+    if (!BAND && (a.tx & 3) == 0) {
         const int Tq = a.T >> 2, bw = a.tx >> 2;
         const int q = (int)blockIdx.x / Tq, i = (int)blockIdx.x - q * Tq;
         const int i2 = (int)(((int64_t)i * a.tile_mult) % Tq);
@@ -1268,7 +1280,7 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     const uint32_t r_lo = 0, r_hi = recmap_build(M, a, tile, C_THREADS, L.owner);
     if (r_hi > (uint32_t)a.heavy_min) {                     // bev_tile_cells_heavy's
         if (threadIdx.x == 0) heavy_push(a, tile, r_hi);
-        cells_drain<I64>(a, L, s_buf, true);
+        cells_drain<I64, BAND>(a, L, s_buf, true);
         return;
     }
 
@@ -1381,8 +1393,8 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
         __syncthreads();
     }
     DBG_STAMP(16, 6);
-    tile_finalize_write(a, L.S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
-    cells_drain<I64>(a, L, s_buf, false);
+    tile_finalize_write<BAND>(a, L.S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
+    cells_drain<I64, BAND>(a, L, s_buf, false);
     if ((a.dbg & 16) && threadIdx.x == 0 && tile < 1024) {
         g_dbg_stamps[tile][0] = t_begin; g_dbg_stamps[tile][1] = wall_clock64(); g_dbg_stamps[tile][2] = r_hi - r_lo;
         uint32_t big = 0;
@@ -1462,7 +1474,7 @@ __device__ __forceinline__ void tile_cell_medians32(TileStats &S, uint32_t (*his
 
 // EXTRA (the opt-in reducers) and OWN (an item walks its own half's records: a.split) are template parameters: the kernel
 // sits at the 128-VGPR limit of a 1024-thread workgroup and spilled 4-9 registers with them as run-time flags.
-template <bool I64, bool EXTRA, bool OWN>
+template <bool I64, bool EXTRA, bool OWN, bool BAND = false>
 __device__ __forceinline__ void bev_tile_cells_heavy_body(const BevArgs &a)
 {
     unsigned long long t_begin = wall_clock64();
@@ -1580,7 +1592,7 @@ __device__ __forceinline__ void bev_tile_cells_heavy_body(const BevArgs &a)
         tile_cell_medians32<I64, H_THREADS>(L.S, L.hist, L.M, a, cell, r_lo, r_hi);
     }
     __syncthreads();
-    tile_finalize_write(a, L.S, reinterpret_cast<double(*)[TCELLS]>(smem), tile, H_THREADS, half * H_CELLS, (half + 1) * H_CELLS);
+    tile_finalize_write<BAND>(a, L.S, reinterpret_cast<double(*)[TCELLS]>(smem), tile, H_THREADS, half * H_CELLS, (half + 1) * H_CELLS);
     __syncthreads();                                        // the staging area is the next item's histogram
     if ((a.dbg & 8) && threadIdx.x == 0 && tile < 1024) {
         g_dbg_stamps[tile][0] = t_begin; g_dbg_stamps[tile][1] = wall_clock64(); g_dbg_stamps[tile][2] = r_hi - r_lo;
@@ -1678,6 +1690,30 @@ __global__ __launch_bounds__(H_THREADS) void bev_tile_cells_heavy_many()
 {
     bev_tile_cells_heavy_body<I64, false, false>(g_bev_many[blockIdx.y]);
 }
+// ---- banded rasters (px > 1024): the same kernels over one band of tile rows (a.band_r0, a.band_rows), one launch of each per
+// band.  Separate instantiations, so that the whole-grid kernels above compile to the code they had before bands existed.
+template <bool I64>
+__global__ __launch_bounds__(AB_THREADS) __attribute__((amdgpu_waves_per_eu(BIN_WPE, BIN_WPE))) void bev_tile_bin_band(const BevArgs a) { bev_tile_bin_body<I64, true>(a); }
+template <bool I64>
+__global__ __launch_bounds__(C_THREADS) C_OCC void bev_tile_cells_band(const BevArgs a) { bev_tile_cells_body<I64, true>(a); }
+template <bool I64, bool EXTRA>
+__global__ __launch_bounds__(H_THREADS) void bev_tile_cells_heavy_band(const BevArgs a) { bev_tile_cells_heavy_body<I64, EXTRA, false, true>(a); }
+template <bool I64>
+__global__ __launch_bounds__(AB_THREADS) __attribute__((amdgpu_waves_per_eu(BIN_WPE, BIN_WPE))) void bev_tile_bin_band_many()
+{
+    const BevArgs &a = g_bev_many[blockIdx.y];
+    if ((int)blockIdx.x < a.G) bev_tile_bin_body<I64, true>(a);
+}
+template <bool I64>
+__global__ __launch_bounds__(C_THREADS) C_OCC void bev_tile_cells_band_many()
+{
+    bev_tile_cells_body<I64, true>(g_bev_many[blockIdx.y]);
+}
+template <bool I64>
+__global__ __launch_bounds__(H_THREADS) void bev_tile_cells_heavy_band_many()
+{
+    bev_tile_cells_heavy_body<I64, false, false, true>(g_bev_many[blockIdx.y]);
+}
 
 // ---------------------------------------------------------------------------------------------
 // C ABI
@@ -1686,6 +1722,29 @@ int pca_k1_prepare_pending(pca_ctx *ctx, K1Args *out, int *n_tiles, hipStream_t 
 void pca_k1_pending_launched(pca_ctx *ctx, hipStream_t s);
 static inline int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
 static inline int tiles_x(int px) { return (px + TS - 1) / TS; }
+// Banded rasters.  Level 1 keeps a histogram entry and a cursor per tile in LDS (8 B): 128 KiB for the 16 384 tiles of a
+// 1024^2 grid.  Larger grids (up to 4096^2) run as bands of whole tile rows of at most BAND_TILES tiles each, one level-1 pass
+// over the window and one launch of the tile kernels per band: 2048^2 = 4 bands of 64 tile rows, 4096^2 = 16 of 32.
+#define PX_MAX 4096
+#define BAND_TILES 16384
+static inline int band_rows(int px) { const int tx = tiles_x(px); return tx * tx <= BAND_TILES ? tx : BAND_TILES / tx; }
+// bev_tile_cells: the workgroup -> tile permutation's multiplier, coprime to its period Tp
+static int bev_tile_mult(int Tp)
+{
+    auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
+    int m = (int)(Tp * 0.6180339887) | 1;
+    while (m > 1 && gcd(m, Tp) != 1) m -= 2;
+    return m < 1 ? 1 : m;
+}
+// one band of a banded raster: tile rows [r0, r0 + band_rows(px)) of the grid, the last band what is left
+static void bev_set_band(BevArgs &a, int r0)
+{
+    const int rows = band_rows(a.prm.px);
+    a.band_r0 = r0;
+    a.band_rows = a.tx - r0 < rows ? a.tx - r0 : rows;
+    a.T = a.band_rows * a.tx;
+    a.tile_mult = bev_tile_mult(a.T);                       // (bev_tile_cells_body<.., BAND>: one permutation of all the band's tiles)
+}
 // PCA_BEV_G / PCA_BEV_CHUNK: tuning overrides, read on every call (tests switch them to force the memory path)
 static inline int max_groups()
 {
@@ -1708,7 +1767,7 @@ extern "C" {
 int64_t pca_bev_workspace_bytes(int64_t max_points, int px)
 {
     if (max_points < 1) max_points = 1;
-    const int64_t T = (int64_t)tiles_x(px) * tiles_x(px), G = n_groups(max_points);
+    const int64_t T = (int64_t)band_rows(px) * tiles_x(px), G = n_groups(max_points);   // (the tiles of one band: all of them up to 1024^2)
     return align256(max_points * 4) + 3 * align256((G + K1_RIDE + 8) * T * 4) + align256((HQ_IDS + HQ_CLASSES * T) * 4) +
            align256((max_points + G + K1_RIDE + K1_SEG) * 24) + 512;
 }
@@ -1752,7 +1811,7 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
         return -1;
     }
     if (!store || !frame_off || !prm || !workspace || (!planes && !planes_f16)) { ctx->err = "bev: bad arguments"; return -1; }
-    if (prm->px < 1 || prm->px > 1024) { ctx->err = "bev: px must be in 1..1024"; return -1; }
+    if (prm->px < 1 || prm->px > PX_MAX) { ctx->err = "bev: px must be in 1..4096"; return -1; }
     // the elevation plane is min(z - origin_z): the rotation has to leave z alone (rotation_matrix_3d of the reference)
     if (!(prm->R[6] == 0.0 && prm->R[7] == 0.0 && prm->R[8] == 1.0 && prm->R[2] == 0.0 && prm->R[5] == 0.0)) {
         ctx->err = "bev: R must be a rotation about the z axis (R[2] = R[5] = R[6] = R[7] = 0, R[8] = 1)";
@@ -1779,7 +1838,9 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
         for (int i = 0; i < 12; ++i) a.pend_T[k].m[i] = pending_Ts[16 * k + i];
     }
     a.tx = tiles_x(prm->px);
-    a.T = a.tx * a.tx;
+    a.band_rows = band_rows(prm->px);                       // (< tx: a banded raster, bev_set_band picks the band)
+    a.band_r0 = 0;
+    a.T = a.band_rows * a.tx;                               // (the workspace's layout: the largest band)
     a.G = n_groups(max_points);
     bev_table_order(a);
     char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
@@ -1799,13 +1860,7 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     { static int dbg = -1; if (dbg < 0) { const char *e = getenv("PCA_BEV_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
     { static int sg = -1; if (sg < 0) { const char *e = getenv("PCA_BEV_STAGGER"); sg = e ? atoi(e) : 0; if (sg < 0 || sg > 64) sg = 0; } a.stagger = sg; }
     a.status = ctx->ticket + 1;
-    {
-        auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
-        const int Tp = (a.tx & 3) == 0 ? a.T / 4 : a.T;     // the permutation's period (bev_tile_cells_body)
-        int m = (int)(Tp * 0.6180339887) | 1;
-        while (m > 1 && gcd(m, Tp) != 1) m -= 2;
-        a.tile_mult = m < 1 ? 1 : m;
-    }
+    a.tile_mult = bev_tile_mult((a.tx & 3) == 0 ? a.T / 4 : a.T);   // the permutation's period (bev_tile_cells_body)
     a.heavy_hint = nullptr; a.heavy_hint_known = 0; a.heavy_launched = 1;
     a.span_hint = nullptr; a.span_hint_known = 0;
     return 0;
@@ -1828,8 +1883,61 @@ static int bev_set_lds_attributes(pca_ctx *ctx)
     PCA_BEV_LDS_ATTR(bev_tile_bin<true>, 128 * 1024);
     PCA_BEV_LDS_ATTR(bev_tile_bin_many<false>, 128 * 1024);
     PCA_BEV_LDS_ATTR(bev_tile_bin_many<true>, 128 * 1024);
+    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<false, false>), HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<false, true>), HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<true, false>), HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<true, true>), HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_band_many<false>, HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_band_many<true>, HEAVY_LDS_BYTES);
+    PCA_BEV_LDS_ATTR(bev_tile_bin_band<false>, BAND_TILES * 8);
+    PCA_BEV_LDS_ATTR(bev_tile_bin_band<true>, BAND_TILES * 8);
+    PCA_BEV_LDS_ATTR(bev_tile_bin_band_many<false>, BAND_TILES * 8);
+    PCA_BEV_LDS_ATTR(bev_tile_bin_band_many<true>, BAND_TILES * 8);
 #undef PCA_BEV_LDS_ATTR
     lds_set = true;
+    return 0;
+}
+
+// pca_bev_generate_chain for px > 1024: a.band_rows < a.tx, bev_prepare done.  Every band is one level-1 pass over the window and
+// the tile kernels over the band's tiles, in the caller's planes; all bands share the workspace, one after the other on `s`.
+// Owed transforms: with write_back, band 0 applies and stores them and the later bands read the updated store (n_pend = 0);
+// without, every band applies them on the fly.  Every per-cell statistic depends on the cell's own points only: the planes
+// equal those of any other banding.
+static int bev_generate_banded(pca_ctx *ctx, BevArgs &a, bool bin_given, int bin_first, int bin_end, hipStream_t s)
+{
+    if (pca_k1_flush_pending(ctx)) return -1;
+    a.heavy_launched = 1;
+    a.split = 0;
+    if (bin_given && !(a.n_pend > 0 && a.write_back)) {      // (as the whole-grid call: never with a write-back; PCA_BEV_CULL=0: ignored)
+        static int cu = -1;
+        if (cu < 0) { const char *e = getenv("PCA_BEV_CULL"); cu = e ? atoi(e) : 1; }
+        if (cu) {
+            int f = bin_first > a.slot_begin ? bin_first : a.slot_begin, e = bin_end < a.slot_end ? bin_end : a.slot_end;
+            if (e < f) e = f;
+            a.bin_first = f; a.bin_end = e;
+        }
+    }
+    const size_t lds = (size_t)a.T * 8;                     // (the largest band's)
+    if (ctx->profiling == 2) pca_prof_begin(ctx, PCA_K_BEV_UNIT, s);
+    const int rows = a.band_rows;
+    for (int r0 = 0; r0 < a.tx; r0 += rows) {
+        bev_set_band(a, r0);
+        if (r0 > 0 && a.write_back) a.n_pend = 0;           // band 0 has stored them
+        const int heavy_grid = a.T < ctx->n_cu ? a.T : ctx->n_cu;
+        if (a.intensity64) {
+            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_band<true>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
+            PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells_band<true>, dim3(a.T), dim3(C_THREADS), s, a);
+            if (a.extra) PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<true, true>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
+            else PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<true, false>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
+        } else {
+            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_band<false>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
+            PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells_band<false>, dim3(a.T), dim3(C_THREADS), s, a);
+            if (a.extra) PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<false, true>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
+            else PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<false, false>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
+        }
+    }
+    if (ctx->profiling == 2) pca_prof_end(ctx, s);
+    PCA_CHECK(ctx, hipGetLastError());
     return 0;
 }
 
@@ -1851,6 +1959,11 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
                     pending_slot_ends, n_pending, write_back, workspace, workspace_bytes, planes, planes_f16, extra_planes, a))
         return -1;
     if (bev_set_lds_attributes(ctx)) return -1;
+    // A banded raster (px > 1024: bev_set_band) takes the simple choices where the whole-grid one tunes for speed: the heavy
+    // kernel follows every band (no heavy_hint, no cooldown), the pieces are not ordered by halves of tiles (a band has more
+    // tiles than level 1's LDS holds twice), a bin range applies to every band but never makes a one-round launch (no
+    // span_hint), and a deferred K1 never rides along (it runs on its own first).
+    if (a.band_rows < a.tx) return bev_generate_banded(ctx, a, bin_given, bin_first, bin_end, s);
     // one resident workgroup per CU draws from the queue -- when the previous call had no heavy tile (uniform data)
     // only a few are launched: any number of them drains the queue, and 256 idle 110-KiB workgroups cost ~5 us
     const int heavy_grid = a.T < ctx->n_cu ? a.T : ctx->n_cu;
@@ -1975,10 +2088,14 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     const int px = jobs[0].prm.px;
+    if (px < 1 || px > PX_MAX) { ctx->err = "bev: px must be in 1..4096"; return -1; }
     const int64_t per = (pca_bev_workspace_bytes(max_points, px) + 255) & ~255ll;
     if (workspace_bytes < per * n_jobs + 256) { ctx->err = "bev: workspace too small for this many rasters"; return -1; }
+    // banded rasters (px > 1024): one argument block per (band, job), band-major; the bands run one after the other, each
+    // for all the jobs (every job keeps its own workspace slice)
+    const int rows = band_rows(px), n_bands = (tiles_x(px) + rows - 1) / rows;
     // argument blocks: built in pinned memory, copied to the constant array PCA_BEV_MANY_MAX samples at a time
-    const int64_t up_bytes = (int64_t)sizeof(BevArgs) * n_jobs;
+    const int64_t up_bytes = (int64_t)sizeof(BevArgs) * n_jobs * n_bands;
     if (ctx->bevm_busy) { PCA_CHECK(ctx, hipEventSynchronize(ctx->bevm_ev)); ctx->bevm_busy = false; }
     if (up_bytes > ctx->bevm_cap) {
         if (ctx->bevm_pin) PCA_CHECK(ctx, hipHostFree(ctx->bevm_pin));
@@ -1998,10 +2115,14 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
             return -1;
         G = ha[k].G; T = ha[k].T;
     }
+    for (int b = n_bands - 1; b >= 0 && n_bands > 1; --b)  // (backwards: band 0 is built in place from the blocks above)
+        for (int k = 0; k < n_jobs; ++k) {
+            BevArgs &d = ha[(int64_t)b * n_jobs + k];
+            d = ha[k];
+            bev_set_band(d, b * rows);
+        }
     if (bev_set_lds_attributes(ctx)) return -1;
     const size_t lds = (size_t)T * 8;
-    // a few resident workgroups per sample drain whatever heavy tiles there are (any number of them does)
-    const int heavy_grid = T < 8 ? T : 8;
     // The argument blocks live in ONE constant array per device (g_bev_many): a call on another stream or from another
     // context of this device must not overwrite it while this call's kernels may still read it.  Calls take turns on the
     // host (mutex) and on the device (every call first waits for the event the previous one recorded behind its kernels).
@@ -2012,8 +2133,13 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
     if (last) PCA_CHECK(ctx, hipStreamWaitEvent(s, last, 0));
     else PCA_CHECK(ctx, hipEventCreateWithFlags(&last, hipEventDisableTiming));
     if (ctx->profiling) pca_prof_begin(ctx, PCA_K_BEV_UNIT, s);
-    for (int k0 = 0; k0 < n_jobs; k0 += PCA_BEV_MANY_MAX) {
-        const int nk = n_jobs - k0 < PCA_BEV_MANY_MAX ? n_jobs - k0 : PCA_BEV_MANY_MAX;
+    for (int b = 0; b < n_bands; ++b)
+    for (int j0 = 0; j0 < n_jobs; j0 += PCA_BEV_MANY_MAX) {
+        const int nk = n_jobs - j0 < PCA_BEV_MANY_MAX ? n_jobs - j0 : PCA_BEV_MANY_MAX;
+        const int64_t k0 = (int64_t)b * n_jobs + j0;        // (the blocks of band b)
+        const int Tb = ha[k0].T;                            // (the band's tiles: the same for every job)
+        // a few resident workgroups per sample drain whatever heavy tiles there are (any number of them does)
+        const int heavy_grid = Tb < 8 ? Tb : 8;
         // (the argument blocks, 1.3 KB per sample: fetched by a kernel from the mapped host block instead of a copy command,
         // see pca_fetch_block; PCA_SMALL_COPY=1 restores the copy for A/B)
         static int small_copy = -1;
@@ -2022,7 +2148,17 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
         if (!many_dev[ctx->device & 63]) PCA_CHECK(ctx, hipGetSymbolAddress(&many_dev[ctx->device & 63], HIP_SYMBOL(g_bev_many)));
         if (small_copy) PCA_CHECK(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_bev_many), ha + k0, sizeof(BevArgs) * (size_t)nk, 0, hipMemcpyHostToDevice, s));
         else if (pca_fetch_block(ctx, ha, (int64_t)sizeof(BevArgs) * k0, many_dev[ctx->device & 63], (int64_t)sizeof(BevArgs) * nk, s)) return -1;
-        if (intensity64) {
+        if (n_bands > 1) {
+            if (intensity64) {
+                hipLaunchKernelGGL(bev_tile_bin_band_many<true>, dim3(G, nk), dim3(AB_THREADS), lds, s);
+                hipLaunchKernelGGL(bev_tile_cells_band_many<true>, dim3(Tb, nk), dim3(C_THREADS), 0, s);
+                hipLaunchKernelGGL(bev_tile_cells_heavy_band_many<true>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
+            } else {
+                hipLaunchKernelGGL(bev_tile_bin_band_many<false>, dim3(G, nk), dim3(AB_THREADS), lds, s);
+                hipLaunchKernelGGL(bev_tile_cells_band_many<false>, dim3(Tb, nk), dim3(C_THREADS), 0, s);
+                hipLaunchKernelGGL(bev_tile_cells_heavy_band_many<false>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
+            }
+        } else if (intensity64) {
             hipLaunchKernelGGL(bev_tile_bin_many<true>, dim3(G, nk), dim3(AB_THREADS), lds, s);
             hipLaunchKernelGGL(bev_tile_cells_many<true>, dim3(T, nk), dim3(C_THREADS), 0, s);
             hipLaunchKernelGGL(bev_tile_cells_heavy_many<true>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
