@@ -823,9 +823,7 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
     if (ctx->profiling == 1) pca_prof_begin(ctx, PCA_K_NUSC, s);
     // (descriptors + tile table, ~20 KB: fetched by a kernel from the mapped host block -- a copy command of this size was
     // 13-17 us of a 60-95 us call; PCA_SMALL_COPY=1 restores it for A/B)
-    static int small_copy = -1;
-    if (small_copy < 0) { const char *e = getenv("PCA_SMALL_COPY"); small_copy = e ? atoi(e) : 0; }
-    if (small_copy) PCA_CHECK(ctx, hipMemcpyAsync(ctx->k1n_desc_dev, ctx->k1n_pin, (size_t)up_bytes, hipMemcpyHostToDevice, s));
+    if (pca_small_copy()) PCA_CHECK(ctx, hipMemcpyAsync(ctx->k1n_desc_dev, ctx->k1n_pin, (size_t)up_bytes, hipMemcpyHostToDevice, s));
     else if (pca_fetch_block(ctx, ctx->k1n_pin, 0, ctx->k1n_desc_dev, up_bytes, s)) return -1;
     PCA_CHECK(ctx, hipEventRecord(ctx->k1n_ev, s));
     ctx->k1n_busy = true;

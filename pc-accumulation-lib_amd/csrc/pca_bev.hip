@@ -1727,6 +1727,9 @@ static inline int tiles_x(int px) { return (px + TS - 1) / TS; }
 // over the window and one launch of the tile kernels per band: 2048^2 = 4 bands of 64 tile rows, 4096^2 = 16 of 32.
 #define PX_MAX 4096
 #define BAND_TILES 16384
+#define BEV_STR_(x) #x
+#define BEV_STR(x) BEV_STR_(x)
+#define PX_CHECK(ctx, px) do { if ((px) < 1 || (px) > PX_MAX) { (ctx)->err = "bev: px must be in 1.." BEV_STR(PX_MAX); return -1; } } while (0)
 static inline int band_rows(int px) { const int tx = tiles_x(px); return tx * tx <= BAND_TILES ? tx : BAND_TILES / tx; }
 // bev_tile_cells: the workgroup -> tile permutation's multiplier, coprime to its period Tp
 static int bev_tile_mult(int Tp)
@@ -1746,31 +1749,60 @@ static void bev_set_band(BevArgs &a, int r0)
     a.tile_mult = bev_tile_mult(a.T);                       // (bev_tile_cells_body<.., BAND>: one permutation of all the band's tiles)
 }
 // PCA_BEV_G / PCA_BEV_CHUNK: tuning overrides, read on every call (tests switch them to force the memory path)
-static inline int max_groups()
-{
-    const char *e = getenv("PCA_BEV_G");
-    const int max_g = e ? atoi(e) : MAX_G;
-    return (max_g < 1 || max_g > 1024) ? MAX_G : max_g;
-}
+static inline int max_groups() { return (int)pca_env_int("PCA_BEV_G", MAX_G, 1, 1024); }
 static inline int n_groups(int64_t max_points)
 {
-    const char *c = getenv("PCA_BEV_CHUNK");
-    const int max_g = max_groups();
-    int per_g = c ? atoi(c) : 8192;
-    if (per_g < 1024) per_g = 8192;
+    const int max_g = max_groups(), per_g = (int)pca_env_int("PCA_BEV_CHUNK", 8192, 1024);
     int64_t g = (max_points + per_g - 1) / per_g;
     return (int)(g < 1 ? 1 : (g > max_g ? max_g : g));
 }
 
-extern "C" {
-
-int64_t pca_bev_workspace_bytes(int64_t max_points, int px)
+// The workspace of one raster: the byte offsets of its regions from the (256-byte aligned) base -- the keys come first, at 0
+// -- and its size, a multiple of 256.  The ONLY place that knows the layout: pca_bev_workspace_bytes returns `total`,
+// bev_prepare places the regions, pca_bev_generate_many steps from raster to raster by `total`.  T = the tiles of one band
+// (all of them up to 1024^2), G = level 1's pieces; the counter tables and the records have room for K1_RIDE riding K1 tiles.
+struct BevLayout { int T, G; int64_t bh, boff, bh0, heavy, recs, total; };
+static BevLayout bev_layout(int64_t max_points, int px)
 {
     if (max_points < 1) max_points = 1;
-    const int64_t T = (int64_t)band_rows(px) * tiles_x(px), G = n_groups(max_points);   // (the tiles of one band: all of them up to 1024^2)
-    return align256(max_points * 4) + 3 * align256((G + K1_RIDE + 8) * T * 4) + align256((HQ_IDS + HQ_CLASSES * T) * 4) +
-           align256((max_points + G + K1_RIDE + K1_SEG) * 24) + 512;
+    const int64_t T = (int64_t)band_rows(px) * tiles_x(px), G = n_groups(max_points);
+    const int64_t table = align256((G + K1_RIDE + 8) * T * 4);                 // bh, boff, bh0: one each
+    BevLayout l;
+    l.T = (int)T; l.G = (int)G;
+    l.bh = align256(max_points * 4);
+    l.boff = l.bh + table; l.bh0 = l.boff + table;
+    l.heavy = l.bh0 + table;
+    l.recs = l.heavy + align256((HQ_IDS + HQ_CLASSES * T) * 4);
+    l.total = l.recs + align256((max_points + G + K1_RIDE + K1_SEG) * 24) + 512;
+    return l;
 }
+
+// Every kernel of the rasteriser the host can launch, by (I64, BAND): g_bev_kernels[intensity64 given][banded raster].
+// bev_set_lds_attributes walks this table, so a kernel that can be launched is a kernel whose LDS ceiling is set.
+// (bev_tile_bin_k1, level 1 with a riding K1, stands next to it: !I64, whole grid only, K1_RIDE_LDS.)
+typedef void (*BevKernel)(BevArgs);
+typedef void (*BevManyKernel)();
+struct BevKernelSet {
+    BevKernel bin, cells, heavy[2][2];                      // heavy[EXTRA][OWN]; null: no such variant (a band is never split)
+    BevManyKernel bin_many, cells_many, heavy_many;         // pca_bev_generate_many: blockIdx.y = sample
+    int bin_lds;                                            // ceiling of level 1's dynamic LDS [bytes]; the heavy kernels': HEAVY_LDS_BYTES
+};
+#define K1_RIDE_LDS (80 * 1024)
+#define BEV_WHOLE_SET(I)                                                                                                          \
+    { bev_tile_bin<I>, bev_tile_cells<I>,                                                                                         \
+      {{bev_tile_cells_heavy<I, false, false>, bev_tile_cells_heavy<I, false, true>}, {bev_tile_cells_heavy<I, true, false>, bev_tile_cells_heavy<I, true, true>}}, \
+      bev_tile_bin_many<I>, bev_tile_cells_many<I>, bev_tile_cells_heavy_many<I>, 128 * 1024 }
+#define BEV_BAND_SET(I)                                                                                                           \
+    { bev_tile_bin_band<I>, bev_tile_cells_band<I>,                                                                               \
+      {{bev_tile_cells_heavy_band<I, false>, nullptr}, {bev_tile_cells_heavy_band<I, true>, nullptr}},                           \
+      bev_tile_bin_band_many<I>, bev_tile_cells_band_many<I>, bev_tile_cells_heavy_band_many<I>, BAND_TILES * 8 }
+static const BevKernelSet g_bev_kernels[2][2] = {{BEV_WHOLE_SET(false), BEV_BAND_SET(false)}, {BEV_WHOLE_SET(true), BEV_BAND_SET(true)}};
+#undef BEV_WHOLE_SET
+#undef BEV_BAND_SET
+
+extern "C" {
+
+int64_t pca_bev_workspace_bytes(int64_t max_points, int px) { return bev_layout(max_points, px).total; }
 
 int pca_bev_generate(pca_ctx *ctx, const pca_store *store, const double *intensity64, const int64_t *frame_off,
                      int slot_begin, int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm,
@@ -1792,14 +1824,13 @@ int pca_bev_generate_ex(pca_ctx *ctx, const pca_store *store, const double *inte
                                   extra_planes, stream);
 }
 
-// Checks one raster's arguments and fills the kernels' argument block (everything but the heavy-tile bookkeeping)
 static void bev_table_order(BevArgs &a)
 {   // PCA_BEV_XCD_TABLES=0: the counter tables in plain [tile][workgroup] order (A/B)
-    static int xt = -1;
-    if (xt < 0) { const char *e = getenv("PCA_BEV_XCD_TABLES"); xt = e ? atoi(e) : 1; }
+    const bool xt = PCA_ENV_ONCE("PCA_BEV_XCD_TABLES", 1) != 0;
     a.Gp = (xt && a.G >= 16 && a.G <= 1016) ? (a.G + 7) / 8 : 0;   // (RecMap holds 1024 places)
     a.Gr = a.Gp ? 8 * a.Gp : a.G;
 }
+// Checks one raster's arguments and fills the kernels' argument block (everything but the heavy-tile bookkeeping)
 static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *intensity64, const int64_t *frame_off,
                        int slot_begin, int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm,
                        const double *pending_Ts, const int *pending_slot_ends, int n_pending, int write_back,
@@ -1811,7 +1842,7 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
         return -1;
     }
     if (!store || !frame_off || !prm || !workspace || (!planes && !planes_f16)) { ctx->err = "bev: bad arguments"; return -1; }
-    if (prm->px < 1 || prm->px > PX_MAX) { ctx->err = "bev: px must be in 1..4096"; return -1; }
+    PX_CHECK(ctx, prm->px);
     // the elevation plane is min(z - origin_z): the rotation has to leave z alone (rotation_matrix_3d of the reference)
     if (!(prm->R[6] == 0.0 && prm->R[7] == 0.0 && prm->R[8] == 1.0 && prm->R[2] == 0.0 && prm->R[5] == 0.0)) {
         ctx->err = "bev: R must be a rotation about the z axis (R[2] = R[5] = R[6] = R[7] = 0, R[8] = 1)";
@@ -1819,7 +1850,8 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     }
     if (!(slot_begin <= slot_split && slot_split <= slot_end)) { ctx->err = "bev: need slot_begin <= slot_split <= slot_end"; return -1; }
     if (max_points >= (1ll << 32)) { ctx->err = "bev: window too large for 32-bit positions"; return -1; }
-    if (workspace_bytes < pca_bev_workspace_bytes(max_points, prm->px)) { ctx->err = "bev: workspace too small"; return -1; }
+    const BevLayout l = bev_layout(max_points, prm->px);
+    if (workspace_bytes < l.total) { ctx->err = "bev: workspace too small"; return -1; }
     a.st = *store;
     a.intensity64 = intensity64;
     a.frame_off = frame_off;
@@ -1840,25 +1872,25 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     a.tx = tiles_x(prm->px);
     a.band_rows = band_rows(prm->px);                       // (< tx: a banded raster, bev_set_band picks the band)
     a.band_r0 = 0;
-    a.T = a.band_rows * a.tx;                               // (the workspace's layout: the largest band)
-    a.G = n_groups(max_points);
+    a.T = l.T;                                              // (the workspace's layout: the largest band)
+    a.G = l.G;
     bev_table_order(a);
     char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    a.key = reinterpret_cast<uint32_t *>(w); w += align256(max_points * 4);
-    a.bh = reinterpret_cast<uint32_t *>(w); w += align256((int64_t)(a.G + K1_RIDE + 8) * a.T * 4);
-    a.boff = reinterpret_cast<uint32_t *>(w); w += align256((int64_t)(a.G + K1_RIDE + 8) * a.T * 4);
-    a.bh0 = reinterpret_cast<uint32_t *>(w); w += align256((int64_t)(a.G + K1_RIDE + 8) * a.T * 4);
+    a.key = reinterpret_cast<uint32_t *>(w);
+    a.bh = reinterpret_cast<uint32_t *>(w + l.bh);
+    a.boff = reinterpret_cast<uint32_t *>(w + l.boff);
+    a.bh0 = reinterpret_cast<uint32_t *>(w + l.bh0);
     a.split = 0;
     a.Gk = 0; a.k1_slot = -1; a.k1_n = 0;
     a.bin_first = slot_begin; a.bin_end = slot_end;
-    a.heavy = reinterpret_cast<uint32_t *>(w); w += align256((int64_t)(HQ_IDS + HQ_CLASSES * (int64_t)a.T) * 4);
-    a.recs = w;
+    a.heavy = reinterpret_cast<uint32_t *>(w + l.heavy);
+    a.recs = w + l.recs;
     a.planes = planes;
     a.planes_f16 = planes_f16;
     a.extra = extra_planes;
-    { static int hm = -1; if (hm < 0) { const char *e = getenv("PCA_BEV_HEAVY_MIN"); hm = e ? atoi(e) : HEAVY_MIN_DEFAULT; if (hm < 1 || hm > RGB_CAP) hm = RGB_CAP; } a.heavy_min = hm; }
-    { static int dbg = -1; if (dbg < 0) { const char *e = getenv("PCA_BEV_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
-    { static int sg = -1; if (sg < 0) { const char *e = getenv("PCA_BEV_STAGGER"); sg = e ? atoi(e) : 0; if (sg < 0 || sg > 64) sg = 0; } a.stagger = sg; }
+    { const int hm = (int)PCA_ENV_ONCE("PCA_BEV_HEAVY_MIN", HEAVY_MIN_DEFAULT); a.heavy_min = (hm < 1 || hm > RGB_CAP) ? RGB_CAP : hm; }
+    a.dbg = (int)PCA_ENV_ONCE("PCA_BEV_DBG", 0);
+    a.stagger = (int)PCA_ENV_ONCE("PCA_BEV_STAGGER", 0, 0, 64);
     a.status = ctx->ticket + 1;
     a.tile_mult = bev_tile_mult((a.tx & 3) == 0 ? a.T / 4 : a.T);   // the permutation's period (bev_tile_cells_body)
     a.heavy_hint = nullptr; a.heavy_hint_known = 0; a.heavy_launched = 1;
@@ -1870,74 +1902,133 @@ static int bev_set_lds_attributes(pca_ctx *ctx)
 {
     static bool lds_set = false;                            // > 64 KiB of dynamic LDS has to be asked for once
     if (lds_set) return 0;
-#define PCA_BEV_LDS_ATTR(k, bytes) PCA_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&(k)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
-#define PCA_BEV_HEAVY_ATTR(I) PCA_BEV_LDS_ATTR((bev_tile_cells_heavy<I, false, false>), HEAVY_LDS_BYTES); PCA_BEV_LDS_ATTR((bev_tile_cells_heavy<I, false, true>), HEAVY_LDS_BYTES); \
-    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy<I, true, false>), HEAVY_LDS_BYTES); PCA_BEV_LDS_ATTR((bev_tile_cells_heavy<I, true, true>), HEAVY_LDS_BYTES)
-    PCA_BEV_HEAVY_ATTR(false);
-    PCA_BEV_HEAVY_ATTR(true);
-#undef PCA_BEV_HEAVY_ATTR
-    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_many<false>, HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_many<true>, HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_k1, 80 * 1024);
-    PCA_BEV_LDS_ATTR(bev_tile_bin<false>, 128 * 1024);
-    PCA_BEV_LDS_ATTR(bev_tile_bin<true>, 128 * 1024);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_many<false>, 128 * 1024);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_many<true>, 128 * 1024);
-    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<false, false>), HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<false, true>), HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<true, false>), HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR((bev_tile_cells_heavy_band<true, true>), HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_band_many<false>, HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR(bev_tile_cells_heavy_band_many<true>, HEAVY_LDS_BYTES);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_band<false>, BAND_TILES * 8);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_band<true>, BAND_TILES * 8);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_band_many<false>, BAND_TILES * 8);
-    PCA_BEV_LDS_ATTR(bev_tile_bin_band_many<true>, BAND_TILES * 8);
-#undef PCA_BEV_LDS_ATTR
+    auto grant = [](auto k, size_t bytes) { return k ? hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess; };
+    for (int i = 0; i < 4; ++i) {
+        const BevKernelSet &ks = g_bev_kernels[i >> 1][i & 1];
+        PCA_CHECK(ctx, grant(ks.bin, ks.bin_lds));
+        PCA_CHECK(ctx, grant(ks.bin_many, ks.bin_lds));
+        for (int v = 0; v < 4; ++v) PCA_CHECK(ctx, grant(ks.heavy[v >> 1][v & 1], HEAVY_LDS_BYTES));
+        PCA_CHECK(ctx, grant(ks.heavy_many, HEAVY_LDS_BYTES));
+    }
+    PCA_CHECK(ctx, grant(bev_tile_bin_k1, K1_RIDE_LDS));
     lds_set = true;
     return 0;
 }
 
-// pca_bev_generate_chain for px > 1024: a.band_rows < a.tx, bev_prepare done.  Every band is one level-1 pass over the window and
-// the tile kernels over the band's tiles, in the caller's planes; all bands share the workspace, one after the other on `s`.
-// Owed transforms: with write_back, band 0 applies and stores them and the later bands read the updated store (n_pend = 0);
-// without, every band applies them on the fly.  Every per-cell statistic depends on the cell's own points only: the planes
-// equal those of any other banding.
-static int bev_generate_banded(pca_ctx *ctx, BevArgs &a, bool bin_given, int bin_first, int bin_end, hipStream_t s)
+// ---- the decisions of one pca_bev_generate_chain call, in the order they are taken.  `tuned`: a whole-grid raster
+// (px <= 1024).  A banded raster (px > 1024: bev_set_band) takes the simple choice where the whole-grid one tunes for speed:
+// the heavy kernel follows every band (no heavy_hint, no cooldown), the pieces are not ordered by halves of tiles (a band
+// has more tiles than level 1's LDS holds twice), a deferred K1 never rides along (it runs on its own first), and a bin
+// range applies to every band but never makes a one-round launch (no span_hint). ----
+// Heavy launch and cooldown.
+static void bev_decide_heavy(pca_ctx *ctx, BevArgs &a, bool tuned)
 {
-    if (pca_k1_flush_pending(ctx)) return -1;
-    a.heavy_launched = 1;
-    a.split = 0;
-    if (bin_given && !(a.n_pend > 0 && a.write_back)) {      // (as the whole-grid call: never with a write-back; PCA_BEV_CULL=0: ignored)
-        static int cu = -1;
-        if (cu < 0) { const char *e = getenv("PCA_BEV_CULL"); cu = e ? atoi(e) : 1; }
-        if (cu) {
-            int f = bin_first > a.slot_begin ? bin_first : a.slot_begin, e = bin_end < a.slot_end ? bin_end : a.slot_end;
-            if (e < f) e = f;
-            a.bin_first = f; a.bin_end = e;
-        }
-    }
-    const size_t lds = (size_t)a.T * 8;                     // (the largest band's)
-    if (ctx->profiling == 2) pca_prof_begin(ctx, PCA_K_BEV_UNIT, s);
-    const int rows = a.band_rows;
-    for (int r0 = 0; r0 < a.tx; r0 += rows) {
-        bev_set_band(a, r0);
-        if (r0 > 0 && a.write_back) a.n_pend = 0;           // band 0 has stored them
-        const int heavy_grid = a.T < ctx->n_cu ? a.T : ctx->n_cu;
-        if (a.intensity64) {
-            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_band<true>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
-            PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells_band<true>, dim3(a.T), dim3(C_THREADS), s, a);
-            if (a.extra) PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<true, true>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
-            else PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<true, false>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
-        } else {
-            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_band<false>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
-            PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells_band<false>, dim3(a.T), dim3(C_THREADS), s, a);
-            if (a.extra) PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<false, true>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
-            else PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy_band<false, false>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
-        }
-    }
-    if (ctx->profiling == 2) pca_prof_end(ctx, s);
-    PCA_CHECK(ctx, hipGetLastError());
+    if (!tuned) return;                                     // (bev_prepare: launched, no hint)
+    a.heavy_hint = ctx->heavy_hint_dev;
+    a.heavy_hint_known = *ctx->heavy_hint;
+    // the heavy kernel is launched while heavy tiles were seen in one of the last 64 calls (a tile hovering around the
+    // threshold must not pay the light kernel's slow path every other call); PCA_BEV_HEAVY_ALWAYS=1: regardless (A/B)
+    if (a.heavy_hint_known != 0) ctx->heavy_cooldown = 64;
+    else if (ctx->heavy_cooldown > 0) --ctx->heavy_cooldown;
+    a.heavy_launched = a.heavy_hint_known != 0 || ctx->heavy_cooldown > 0;
+    if (PCA_ENV_ONCE("PCA_BEV_HEAVY_ALWAYS", 0)) a.heavy_launched = 1;
+}
+
+// Split halves; returns level 1's dynamic LDS (histogram + cursors; a banded raster: of the largest band).
+static size_t bev_decide_split(BevArgs &a, bool tuned)
+{
+    // Pieces ordered by half of the tile when the heavy kernel follows (its items are halves), level 1's LDS holds 2 T histogram
+    // entries + 2 T cursors (px <= 720) AND the window stays on level 1's register path.  On the memory path of giant windows
+    // (BASELINE config 4: 1e8 points, 512^2) it was measured and LOSES: the heavy kernel 1485 -> 1261 us, but level 1 2980 ->
+    // 3420 us -- its scattered 16-byte record stores then feed 8192 open ranges per workgroup instead of 4096, a 128-byte line
+    // takes twice as many iterations to fill and is evicted half-written more often (profiles/r05_experiments/bev_split_halves.txt).
+    // Ring model (register path): heavy kernel 44.3 -> 40.9 us, level 1 +0.7.  PCA_BEV_SPLIT=0 / 2: off / also on the memory path (A/B).
+    // (the host knows only an upper bound of the window: it allows the split -- and sizes level 1's LDS for it -- and the
+    // kernels decide on the window's real size, all of them alike: bev_split)
+    const int sp = tuned ? (int)PCA_ENV_ONCE("PCA_BEV_SPLIT", 1) : 0;
+    a.split = (sp && a.heavy_launched && !a.intensity64 && (size_t)a.T * 16 <= 128 * 1024) ? (sp == 2 ? 2 : 1) : 0;
+    return (size_t)a.T * 8 * (a.split ? 2 : 1);
+}
+
+// K1 ride; *nt = the K1 tiles that ride in level 1's launch (k1a their arguments), 0: none.
+static int bev_decide_k1_ride(pca_ctx *ctx, const BevArgs &a, bool tuned, size_t lds, hipStream_t s, K1Args *k1a, int *nt)
+{
+    // A K1 that pca_kitti_integrate left for this raster (the window's last frame, same store, same stream) rides in level 1's
+    // launch as its first workgroups; any other deferred K1 runs now, on its own.  PCA_FUSE_K1=0: always on its own (A/B).
+    *nt = 0;
+    if (!ctx->k1_pend.valid) return 0;
+    if (!tuned) return pca_k1_flush_pending(ctx);
+    const int fk = (int)PCA_ENV_ONCE("PCA_FUSE_K1", 1);
+    const pca_ctx::K1Pending &pd = ctx->k1_pend;
+    bool owed_ok = true;                                    // (a transform owed by the riding frame itself: its end is not written yet)
+    for (int k = 0; k < a.n_pend; ++k) owed_ok = owed_ok && a.pend_slot_end[k] <= pd.slot;
+    const bool fuse = fk && owed_ok && !a.intensity64 && pd.stream == s && pd.slot == a.slot_end - 1 && pd.slot >= a.slot_begin &&
+                      pd.frame_off == a.frame_off && pd.store.x == a.st.x && lds <= K1_RIDE_LDS && pd.fr.n <= K1_RIDE * K1_SEG &&
+                      pd.fr.n <= a.max_points && pca_k1_prepare_pending(ctx, k1a, nt, s) == 0 && *nt <= K1_RIDE;
+    if (PCA_ENV_ONCE("PCA_FUSE_DBG", 0) && !fuse)           // diagnostics: why a noted K1 ran on its own
+        fprintf(stderr, "bev: K1 of slot %d not taken along: switch %d owed_ok %d i64 %d stream %d slot %d (window %d..%d) frame_off %d store %d lds %zu n %d max_points %lld nt %d\n",
+                pd.slot, fk, (int)owed_ok, a.intensity64 != nullptr, pd.stream == s, pd.slot == a.slot_end - 1, a.slot_begin, a.slot_end,
+                pd.frame_off == a.frame_off, pd.store.x == a.st.x, lds, pd.fr.n, (long long)a.max_points, *nt);
+    if (fuse) return 0;
+    *nt = 0;
+    return pca_k1_flush_pending(ctx);
+}
+
+// Bin range and one-round size; returns the workgroups of a one-round launch of level 1, 0: no such launch.
+struct BevBinRange { bool given; int first, end; };        // (pca_bev_bin_range, as the call found it in the context)
+static int bev_decide_bin_range(pca_ctx *ctx, BevArgs &a, bool tuned, const BevBinRange &r)
+{
+    // The caller's proof of which slots can reach the view (pca_bev_bin_range): good for this call only, and not when this call
+    // writes owed transforms back (a skipped frame could not receive them).  PCA_BEV_CULL=0: ignored (A/B; same results).
+    // With a bin range, ONE round of workgroups if the last such call binned few enough points for level 1's register path at one
+    // piece per CU: a piece costs ~15 us before its first point, two rounds of half-size pieces take almost twice as long as
+    // one (profiles/r05_experiments/bev_cull_frames_out_of_view.txt).  The count comes from the device through a host-visible
+    // word and only sizes the launch: a window that turns out larger goes through the memory path as ever.
+    if (!r.given || !PCA_ENV_ONCE("PCA_BEV_CULL", 1) || (a.n_pend > 0 && a.write_back)) return 0;
+    const int f = r.first > a.slot_begin ? r.first : a.slot_begin, e = r.end < a.slot_end ? r.end : a.slot_end;
+    a.bin_first = f; a.bin_end = e < f ? f : e;
+    if (!tuned) return 0;
+    const int64_t pts = PCA_ENV_ONCE("PCA_BEV_ONE_ROUND_PTS", 14500);
+    a.span_hint = ctx->heavy_hint_dev + 1;
+    a.span_hint_known = ctx->heavy_hint[1];
+    return (pts > 0 && a.span_hint_known != 0 && (int64_t)a.span_hint_known * 1024 <= pts * ctx->n_cu && a.G > ctx->n_cu) ? ctx->n_cu : 0;
+}
+
+// Level 1's grid, once it is known whether nt K1 tiles ride and whether one round of workgroups will do.
+static void bev_size_level1(pca_ctx *ctx, BevArgs &a, int nt, int one_round)
+{
+    if (nt == 0) { if (one_round > 0) { a.G = one_round; bev_table_order(a); } return; }
+    // K1's tiles are pieces 0 .. nt-1, the window's pieces follow: G of them on top (the workspace is sized for G + K1_RIDE) --
+    // unless that exceeds the cap, 512 = two rounds of one workgroup per CU: then the launch stays within those two rounds
+    // and the nt CUs that run a K1 tile first take one window piece less (cap - 2 nt window pieces).  Measured on the
+    // headline, one box, us of level 1 for window pieces + K1 tiles: 512 + 30 63.3 (the 30 start a third round), 482 + 30
+    // 58.0, 450 + 30 56.0, 418 + 30 56.3, 386 + 30 60.4; ring model flat from 354 to 482 (tools/experiments/bev_g_sweep.sh).
+    const pca_ctx::K1Pending &pd = ctx->k1_pend;
+    const int cap = max_groups(), G0 = a.G;
+    if (one_round) one_round -= nt;                         // (K1's tiles hold nt of the CUs when the launch starts)
+    a.G = one_round > 0 ? one_round + nt : (G0 + nt <= cap || (cap - 2 * nt) * 4 < 3 * G0) ? G0 + nt : cap - nt;
+    a.Gk = nt; bev_table_order(a); a.k1_slot = pd.slot; a.k1_n = pd.fr.n;
+    a.max_points = a.max_points - pd.fr.n;                  // the store's part of the window: the riding frame's records come on top
+}
+
+// Launch: one raster, or one band of one -- level 1 (with `k1`: bev_tile_bin_k1, the riding K1's tiles first), the tile
+// kernel, and the heavy kernel if a.heavy_launched.
+// (Running the two tile kernels side by side was tried: a second stream with fork / join events costs ~20 us per
+// call, and hipExtAnyOrderLaunch is not honoured on gfx9 -- see DESIGN.md.)
+static int bev_launch_raster(pca_ctx *ctx, const BevKernelSet &ks, const BevArgs &a, const K1Args *k1, size_t lds, hipStream_t s)
+{
+    if (k1) {
+        PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_k1, dim3(a.G), dim3(AB_THREADS), lds, s, a, *k1);
+        pca_k1_pending_launched(ctx, s);
+    } else PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, ks.bin, dim3(a.G), dim3(AB_THREADS), lds, s, a);
+    PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, ks.cells, dim3(a.T), dim3(C_THREADS), s, a);
+    if (!a.heavy_launched) return 0;
+    // one resident workgroup per CU draws from the queue -- when the previous call had no heavy tile (uniform data)
+    // only a few are launched: any number of them drains the queue, and 256 idle 110-KiB workgroups cost ~5 us
+    const int heavy_grid = a.T < ctx->n_cu ? a.T : ctx->n_cu;
+    const BevKernel heavy = ks.heavy[a.extra != nullptr][a.split != 0];
+    if (!heavy) { ctx->err = "bev: no heavy kernel for a split banded raster"; return -1; }
+    PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, heavy, dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a);
     return 0;
 }
 
@@ -1948,8 +2039,7 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
                            double *extra_planes, void *stream)
 {
     if (!ctx) return -1;
-    const bool bin_given = ctx->bin_valid;                  // (pca_bev_bin_range: for this call, whatever becomes of it)
-    const int bin_first = ctx->bin_first, bin_end = ctx->bin_end;
+    const BevBinRange bin_range = {ctx->bin_valid, ctx->bin_first, ctx->bin_end};   // (for this call, whatever becomes of it)
     ctx->bin_valid = false;
     if (max_points < 1) max_points = 1;
     hipStream_t s = (hipStream_t)stream;
@@ -1959,113 +2049,27 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
                     pending_slot_ends, n_pending, write_back, workspace, workspace_bytes, planes, planes_f16, extra_planes, a))
         return -1;
     if (bev_set_lds_attributes(ctx)) return -1;
-    // A banded raster (px > 1024: bev_set_band) takes the simple choices where the whole-grid one tunes for speed: the heavy
-    // kernel follows every band (no heavy_hint, no cooldown), the pieces are not ordered by halves of tiles (a band has more
-    // tiles than level 1's LDS holds twice), a bin range applies to every band but never makes a one-round launch (no
-    // span_hint), and a deferred K1 never rides along (it runs on its own first).
-    if (a.band_rows < a.tx) return bev_generate_banded(ctx, a, bin_given, bin_first, bin_end, s);
-    // one resident workgroup per CU draws from the queue -- when the previous call had no heavy tile (uniform data)
-    // only a few are launched: any number of them drains the queue, and 256 idle 110-KiB workgroups cost ~5 us
-    const int heavy_grid = a.T < ctx->n_cu ? a.T : ctx->n_cu;
-    a.heavy_hint = ctx->heavy_hint_dev;
-    a.heavy_hint_known = *ctx->heavy_hint;
-    // the heavy kernel is launched while heavy tiles were seen in one of the last 64 calls (a tile hovering around the
-    // threshold must not pay the light kernel's slow path every other call); PCA_BEV_HEAVY_ALWAYS=1: regardless (A/B)
-    if (a.heavy_hint_known != 0) ctx->heavy_cooldown = 64;
-    else if (ctx->heavy_cooldown > 0) --ctx->heavy_cooldown;
-    a.heavy_launched = a.heavy_hint_known != 0 || ctx->heavy_cooldown > 0;
-    { static int always = -1; if (always < 0) { const char *e = getenv("PCA_BEV_HEAVY_ALWAYS"); always = e ? atoi(e) : 0; } if (always) a.heavy_launched = 1; }
-    // Pieces ordered by half of the tile when the heavy kernel follows (its items are halves), level 1's LDS holds 2 T histogram
-    // entries + 2 T cursors (px <= 720) AND the window stays on level 1's register path.  On the memory path of giant windows
-    // (BASELINE config 4: 1e8 points, 512^2) it was measured and LOSES: the heavy kernel 1485 -> 1261 us, but level 1 2980 ->
-    // 3420 us -- its scattered 16-byte record stores then feed 8192 open ranges per workgroup instead of 4096, a 128-byte line
-    // takes twice as many iterations to fill and is evicted half-written more often (profiles/r05_experiments/bev_split_halves.txt).
-    // Ring model (register path): heavy kernel 44.3 -> 40.9 us, level 1 +0.7.  PCA_BEV_SPLIT=0 / 2: off / also on the memory path (A/B).
-    // (the host knows only an upper bound of the window: it allows the split -- and sizes level 1's LDS for it -- and the
-    // kernels decide on the window's real size, all of them alike: bev_split)
-    { static int sp = -1; if (sp < 0) { const char *e = getenv("PCA_BEV_SPLIT"); sp = e ? atoi(e) : 1; }
-      a.split = (sp && a.heavy_launched && !intensity64 && (size_t)a.T * 16 <= 128 * 1024) ? (sp == 2 ? 2 : 1) : 0; }
-    const size_t lds = (size_t)a.T * 8 * (a.split ? 2 : 1);  // bev_tile_bin: histogram + cursors
-    // The caller's proof of which slots can reach the view (pca_bev_bin_range): good for this call only, and not when this call
-    // writes owed transforms back (a skipped frame could not receive them).  PCA_BEV_CULL=0: ignored (A/B; same results).
-    // With a bin range, ONE round of workgroups if the last such call binned few enough points for level 1's register path at one
-    // piece per CU: a piece costs ~15 us before its first point, two rounds of half-size pieces take almost twice as long as
-    // one (profiles/r05_experiments/bev_cull_frames_out_of_view.txt).  The count comes from the device through a host-visible
-    // word and only sizes the launch: a window that turns out larger goes through the memory path as ever.
-    int one_round = 0;
-    if (bin_given) {
-        static int cu = -1;
-        static int64_t pts = -1;
-        if (cu < 0) { const char *e = getenv("PCA_BEV_CULL"); cu = e ? atoi(e) : 1; }
-        if (pts < 0) { const char *e = getenv("PCA_BEV_ONE_ROUND_PTS"); pts = e ? atoll(e) : 14500; }
-        if (cu && !(n_pending > 0 && write_back)) {
-            int f = bin_first > slot_begin ? bin_first : slot_begin, e = bin_end < slot_end ? bin_end : slot_end;
-            if (e < f) e = f;
-            a.bin_first = f; a.bin_end = e;
-            a.span_hint = ctx->heavy_hint_dev + 1;
-            a.span_hint_known = ctx->heavy_hint[1];
-            if (pts > 0 && a.span_hint_known != 0 && (int64_t)a.span_hint_known * 1024 <= pts * ctx->n_cu && a.G > ctx->n_cu) one_round = ctx->n_cu;
-        }
-    }
-    // A K1 that pca_kitti_integrate left for this raster (the window's last frame, same store, same stream) rides in level 1's
-    // launch as its first workgroups; any other deferred K1 runs now, on its own.  PCA_FUSE_K1=0: always on its own (A/B).
-    bool fuse = false;
+    const bool tuned = a.band_rows == a.tx;
+    const BevKernelSet &ks = g_bev_kernels[intensity64 != nullptr][!tuned];
     K1Args k1a;
-    if (ctx->k1_pend.valid) {
-        static int fk = -1;
-        if (fk < 0) { const char *e = getenv("PCA_FUSE_K1"); fk = e ? atoi(e) : 1; }
-        const pca_ctx::K1Pending &pd = ctx->k1_pend;
-        int nt = 0;
-        bool owed_ok = true;                                // (a transform owed by the riding frame itself: its end is not written yet)
-        for (int k = 0; k < n_pending; ++k) owed_ok = owed_ok && pending_slot_ends[k] <= pd.slot;
-        fuse = fk && owed_ok && !intensity64 && pd.stream == s && pd.slot == slot_end - 1 && pd.slot >= slot_begin && pd.frame_off == frame_off &&
-               pd.store.x == store->x && lds <= 80 * 1024 && pd.fr.n <= K1_RIDE * K1_SEG && pd.fr.n <= max_points &&
-               pca_k1_prepare_pending(ctx, &k1a, &nt, s) == 0 && nt <= K1_RIDE;
-        { static int fd = -1; if (fd < 0) { const char *e = getenv("PCA_FUSE_DBG"); fd = e ? atoi(e) : 0; }       // diagnostics: why a noted K1 ran on its own
-          if (fd && !fuse)
-              fprintf(stderr, "bev: K1 of slot %d not taken along: switch %d owed_ok %d i64 %d stream %d slot %d (window %d..%d) frame_off %d store %d lds %zu n %d max_points %lld nt %d\n",
-                      pd.slot, fk, (int)owed_ok, intensity64 != nullptr, pd.stream == s, pd.slot == slot_end - 1, slot_begin, slot_end,
-                      pd.frame_off == frame_off, pd.store.x == store->x, lds, pd.fr.n, (long long)max_points, nt); }
-        // K1's tiles are pieces 0 .. nt-1, the window's pieces follow: G of them on top (the workspace is sized for G + K1_RIDE) --
-        // unless that exceeds the cap, 512 = two rounds of one workgroup per CU: then the launch stays within those two rounds
-        // and the nt CUs that run a K1 tile first take one window piece less (cap - 2 nt window pieces).  Measured on the
-        // headline, one box, us of level 1 for window pieces + K1 tiles: 512 + 30 63.3 (the 30 start a third round), 482 + 30
-        // 58.0, 450 + 30 56.0, 418 + 30 56.3, 386 + 30 60.4; ring model flat from 354 to 482 (tools/experiments/bev_g_sweep.sh).
-        if (fuse) {
-            const int cap = max_groups(), G0 = a.G;
-            if (one_round) one_round -= nt;                     // (K1's tiles hold nt of the CUs when the launch starts)
-            a.G = one_round > 0 ? one_round + nt : (G0 + nt <= cap || (cap - 2 * nt) * 4 < 3 * G0) ? G0 + nt : cap - nt;
-            a.Gk = nt; bev_table_order(a); a.k1_slot = pd.slot; a.k1_n = pd.fr.n;
-            a.max_points = max_points - pd.fr.n;            // the store's part of the window: the riding frame's records come on top
-        }
-        else if (pca_k1_flush_pending(ctx)) return -1;
-    }
-    if (one_round > 0 && !fuse) { a.G = one_round; bev_table_order(a); }
+    int nt = 0;                                             // (the K1 tiles that ride along)
+    bev_decide_heavy(ctx, a, tuned);
+    const size_t lds = bev_decide_split(a, tuned);
+    if (bev_decide_k1_ride(ctx, a, tuned, lds, s, &k1a, &nt)) return -1;
+    const int one_round = bev_decide_bin_range(ctx, a, tuned, bin_range);
+    bev_size_level1(ctx, a, nt, one_round);
+    // A banded raster: every band is one level-1 pass over the window and the tile kernels over the band's tiles, in the caller's
+    // planes; all bands share the workspace, one after the other on `s`.  Owed transforms: with write_back, band 0 applies and
+    // stores them and the later bands read the updated store (n_pend = 0); without, every band applies them on the fly.  Every
+    // per-cell statistic depends on the cell's own points only: the planes equal those of any other banding.
     if (ctx->profiling == 2) pca_prof_begin(ctx, PCA_K_BEV_UNIT, s);
-    // (Running the two tile kernels side by side was tried: a second stream with fork / join events costs ~20 us per
-    // call, and hipExtAnyOrderLaunch is not honoured on gfx9 -- see DESIGN.md.)
-#define PCA_BEV_HEAVY_LAUNCH(I, E, O) PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CELLS_HEAVY, (bev_tile_cells_heavy<I, E, O>), dim3(heavy_grid), dim3(H_THREADS), HEAVY_LDS_BYTES, s, a)
-#define PCA_BEV_HEAVY_PICK(I)                                                                                          \
-    do {                                                                                                               \
-        if (a.extra) { if (a.split) PCA_BEV_HEAVY_LAUNCH(I, true, true); else PCA_BEV_HEAVY_LAUNCH(I, true, false); }  \
-        else { if (a.split) PCA_BEV_HEAVY_LAUNCH(I, false, true); else PCA_BEV_HEAVY_LAUNCH(I, false, false); }        \
-    } while (0)
-    if (intensity64) {
-        PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin<true>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
-        PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells<true>, dim3(a.T), dim3(C_THREADS), s, a);
-        if (a.heavy_launched) PCA_BEV_HEAVY_PICK(true);
-    } else {
-        if (fuse) {
-            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_k1, dim3(a.G), dim3(AB_THREADS), lds, s, a, k1a);
-            pca_k1_pending_launched(ctx, s);
-        } else {
-            PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin<false>, dim3(a.G), dim3(AB_THREADS), lds, s, a);
+    for (int r0 = 0, rows = a.band_rows; r0 < a.tx; r0 += rows) {
+        if (!tuned) {
+            bev_set_band(a, r0);
+            if (r0 > 0 && a.write_back) a.n_pend = 0;       // band 0 has stored them
         }
-        PCA_LAUNCH(ctx, PCA_K_BEV_CELLS, bev_tile_cells<false>, dim3(a.T), dim3(C_THREADS), s, a);
-        if (a.heavy_launched) PCA_BEV_HEAVY_PICK(false);
+        if (bev_launch_raster(ctx, ks, a, nt ? &k1a : nullptr, lds, s)) return -1;
     }
-#undef PCA_BEV_HEAVY_PICK
-#undef PCA_BEV_HEAVY_LAUNCH
     if (ctx->profiling == 2) pca_prof_end(ctx, s);
     PCA_CHECK(ctx, hipGetLastError());
     return 0;
@@ -2088,12 +2092,14 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     const int px = jobs[0].prm.px;
-    if (px < 1 || px > PX_MAX) { ctx->err = "bev: px must be in 1..4096"; return -1; }
-    const int64_t per = (pca_bev_workspace_bytes(max_points, px) + 255) & ~255ll;
+    PX_CHECK(ctx, px);
+    const BevLayout l = bev_layout(max_points, px);
+    const int64_t per = l.total;                            // (every raster's slice; a multiple of 256)
     if (workspace_bytes < per * n_jobs + 256) { ctx->err = "bev: workspace too small for this many rasters"; return -1; }
     // banded rasters (px > 1024): one argument block per (band, job), band-major; the bands run one after the other, each
     // for all the jobs (every job keeps its own workspace slice)
     const int rows = band_rows(px), n_bands = (tiles_x(px) + rows - 1) / rows;
+    const BevKernelSet &ks = g_bev_kernels[intensity64 != nullptr][n_bands > 1];
     // argument blocks: built in pinned memory, copied to the constant array PCA_BEV_MANY_MAX samples at a time
     const int64_t up_bytes = (int64_t)sizeof(BevArgs) * n_jobs * n_bands;
     if (ctx->bevm_busy) { PCA_CHECK(ctx, hipEventSynchronize(ctx->bevm_ev)); ctx->bevm_busy = false; }
@@ -2106,14 +2112,12 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
     if (!ctx->bevm_ev) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->bevm_ev, hipEventDisableTiming));
     BevArgs *ha = reinterpret_cast<BevArgs *>(ctx->bevm_pin);
     char *ws = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    int G = 0, T = 0;
     for (int k = 0; k < n_jobs; ++k) {
         const pca_bev_job &j = jobs[k];
         if (j.prm.px != px) { ctx->err = "bev: the rasters of one call share the grid size"; return -1; }
         if (bev_prepare(ctx, store, intensity64, frame_off, j.slot_begin, j.slot_split, j.slot_end, max_points, &j.prm, nullptr,
                         nullptr, 0, 1, ws + per * k, per, j.planes, j.planes_f16, nullptr, ha[k]))
             return -1;
-        G = ha[k].G; T = ha[k].T;
     }
     for (int b = n_bands - 1; b >= 0 && n_bands > 1; --b)  // (backwards: band 0 is built in place from the blocks above)
         for (int k = 0; k < n_jobs; ++k) {
@@ -2122,7 +2126,7 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
             bev_set_band(d, b * rows);
         }
     if (bev_set_lds_attributes(ctx)) return -1;
-    const size_t lds = (size_t)T * 8;
+    const size_t lds = (size_t)l.T * 8;                     // (the largest band's)
     // The argument blocks live in ONE constant array per device (g_bev_many): a call on another stream or from another
     // context of this device must not overwrite it while this call's kernels may still read it.  Calls take turns on the
     // host (mutex) and on the device (every call first waits for the event the previous one recorded behind its kernels).
@@ -2142,31 +2146,13 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
         const int heavy_grid = Tb < 8 ? Tb : 8;
         // (the argument blocks, 1.3 KB per sample: fetched by a kernel from the mapped host block instead of a copy command,
         // see pca_fetch_block; PCA_SMALL_COPY=1 restores the copy for A/B)
-        static int small_copy = -1;
         static void *many_dev[64] = {};
-        if (small_copy < 0) { const char *e = getenv("PCA_SMALL_COPY"); small_copy = e ? atoi(e) : 0; }
         if (!many_dev[ctx->device & 63]) PCA_CHECK(ctx, hipGetSymbolAddress(&many_dev[ctx->device & 63], HIP_SYMBOL(g_bev_many)));
-        if (small_copy) PCA_CHECK(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_bev_many), ha + k0, sizeof(BevArgs) * (size_t)nk, 0, hipMemcpyHostToDevice, s));
+        if (pca_small_copy()) PCA_CHECK(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_bev_many), ha + k0, sizeof(BevArgs) * (size_t)nk, 0, hipMemcpyHostToDevice, s));
         else if (pca_fetch_block(ctx, ha, (int64_t)sizeof(BevArgs) * k0, many_dev[ctx->device & 63], (int64_t)sizeof(BevArgs) * nk, s)) return -1;
-        if (n_bands > 1) {
-            if (intensity64) {
-                hipLaunchKernelGGL(bev_tile_bin_band_many<true>, dim3(G, nk), dim3(AB_THREADS), lds, s);
-                hipLaunchKernelGGL(bev_tile_cells_band_many<true>, dim3(Tb, nk), dim3(C_THREADS), 0, s);
-                hipLaunchKernelGGL(bev_tile_cells_heavy_band_many<true>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
-            } else {
-                hipLaunchKernelGGL(bev_tile_bin_band_many<false>, dim3(G, nk), dim3(AB_THREADS), lds, s);
-                hipLaunchKernelGGL(bev_tile_cells_band_many<false>, dim3(Tb, nk), dim3(C_THREADS), 0, s);
-                hipLaunchKernelGGL(bev_tile_cells_heavy_band_many<false>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
-            }
-        } else if (intensity64) {
-            hipLaunchKernelGGL(bev_tile_bin_many<true>, dim3(G, nk), dim3(AB_THREADS), lds, s);
-            hipLaunchKernelGGL(bev_tile_cells_many<true>, dim3(T, nk), dim3(C_THREADS), 0, s);
-            hipLaunchKernelGGL(bev_tile_cells_heavy_many<true>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
-        } else {
-            hipLaunchKernelGGL(bev_tile_bin_many<false>, dim3(G, nk), dim3(AB_THREADS), lds, s);
-            hipLaunchKernelGGL(bev_tile_cells_many<false>, dim3(T, nk), dim3(C_THREADS), 0, s);
-            hipLaunchKernelGGL(bev_tile_cells_heavy_many<false>, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
-        }
+        hipLaunchKernelGGL(ks.bin_many, dim3(l.G, nk), dim3(AB_THREADS), lds, s);
+        hipLaunchKernelGGL(ks.cells_many, dim3(Tb, nk), dim3(C_THREADS), 0, s);
+        hipLaunchKernelGGL(ks.heavy_many, dim3(heavy_grid, nk), dim3(H_THREADS), HEAVY_LDS_BYTES, s);
     }
     PCA_CHECK(ctx, hipEventRecord(ctx->bevm_ev, s));
     ctx->bevm_busy = true;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -136,6 +137,18 @@ void pca_prof_end(pca_ctx *ctx, hipStream_t s);
             return -1;                                                                         \
         }                                                                                      \
     } while (0)
+
+// Tuning variables (PCA_*, README): an integer from the environment -- `dflt` when the variable is unset and, with a range,
+// when its value lies outside lo..hi.  pca_env_int reads the environment on EVERY call (the variables that tests switch
+// within one process); PCA_ENV_ONCE(...) takes the same arguments and reads once per process, at its first use.
+static inline int64_t pca_env_int(const char *name, int64_t dflt, int64_t lo = INT64_MIN, int64_t hi = INT64_MAX)
+{
+    const char *e = getenv(name);
+    const int64_t v = e ? atoll(e) : dflt;
+    return (v < lo || v > hi) ? dflt : v;
+}
+#define PCA_ENV_ONCE(...) ([]() -> int64_t { static const int64_t v = pca_env_int(__VA_ARGS__); return v; }())
+static inline bool pca_small_copy() { return PCA_ENV_ONCE("PCA_SMALL_COPY", 0) != 0; }   // 1: small argument blocks by a copy command (A/B)
 
 // internal (pca_k1.hip): runs a deferred K1 now, on its own (no-op without one).  Every entry point that reads or writes a
 // store, frame_off or the status word calls it first.

@@ -1139,8 +1139,8 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     a.nn_prev = reinterpret_cast<int32_t *>(w); w += icp_align((int64_t)n_src * 4);
     a.nn_cell = reinterpret_cast<int32_t *>(w); w += icp_align((int64_t)n_src * 4);
     a.nn_slack = reinterpret_cast<float *>(w); w += icp_align((int64_t)n_src * 4);
-    { static int ns = -1; if (ns < 0) { const char *e = getenv("PCA_ICP_NO_SKIP"); ns = e ? atoi(e) : 0; } a.no_skip = ns; }
-    { static int dg = -1; if (dg < 0) { const char *e = getenv("PCA_ICP_DBG"); dg = e ? atoi(e) : 0; } a.dbg = dg; }
+    a.no_skip = (int)PCA_ENV_ONCE("PCA_ICP_NO_SKIP", 0);
+    a.dbg = (int)PCA_ENV_ONCE("PCA_ICP_DBG", 0);
     a.partial = reinterpret_cast<double *>(w); w += icp_align((int64_t)icp_grid(n_src) * ICP_NACC * 8);
     a.n_count_blocks = (n_tgt + ICP_THREADS - 1) / ICP_THREADS;
     a.zr_part = reinterpret_cast<uint32_t *>(w); w += icp_align((int64_t)a.n_count_blocks * 16);

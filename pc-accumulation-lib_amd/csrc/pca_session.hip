@@ -68,8 +68,7 @@ int pca_kitti_integrate(pca_ctx *ctx, const pca_kitti_obs *obs, const double P[1
         // copy on the caller's stream 202-212; one copy stream 182; two copy streams with half the block each 234-240 (the
         // second event hop and two short DMAs cost more than a second SDMA engine returns); 1 MB pieces staged and sent in
         // turn on one copy stream 213-219 (five pool jobs and five copy calls instead of one each).
-        static int64_t side_min = -1;
-        if (side_min < 0) { const char *e = getenv("PCA_H2D_SIDE_MIN"); side_min = e ? atoll(e) : (256ll << 10); }
+        const int64_t side_min = PCA_ENV_ONCE("PCA_H2D_SIDE_MIN", 256ll << 10);
         if (total >= side_min) {
             if (!ctx->h2d_stream[0]) PCA_CHECK(ctx, hipStreamCreateWithFlags(&ctx->h2d_stream[0], hipStreamNonBlocking));
             if (!ctx->h2d_done[0]) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->h2d_done[0], hipEventDisableTiming));
