@@ -358,6 +358,7 @@ ORC_API int orc_bev(const orc_store *st, const double *intensity64, int64_t n, i
         double a = R[0] * x; a = fma(R[1], y, a); a = fma(R[2], z, a);   /* bev_generator.py:227 */
         double b = R[3] * x; b = fma(R[4], y, b); b = fma(R[5], z, b);
         double c = R[6] * x; c = fma(R[7], y, c); c = fma(R[8], z, c);
+        c += 0.0;                                          /* np.matmul sums from +0.0: a z of -0.0 leaves it as +0.0 */
         a += prm->dx;                                      /* :230-231 */
         b += prm->dy;
         int keep = (a > lo) && (a < hi) && (b > lo) && (b < hi);

@@ -71,5 +71,5 @@ __device__ __forceinline__ void finalize_cell(const pca_bev_params &q, uint32_t 
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) out[2 + ch] = (n ? (double)m2[ch] / 2.0 : q.rgb_fill) / 255.0;
     out[5] = (a_d + 1.0) / ((a_d + 1.0) + ((a_all - a_d) + 1.0));          // dirichlet expectation, vehicles
-    out[6] = n ? zmin : 0.0;
+    out[6] = n ? zmin + 0.0 : 0.0;                                          // (the reference's matmul turns a z of -0.0 into +0.0)
 }

@@ -5,6 +5,7 @@ test_pipeline_golden.py (oracle kernels + product host logic)."""
 import numpy as np
 import pytest
 
+from bev_edges_common import EDGE_CASES, EdgeCase
 from oracle import oracle as orc
 
 KITTI_FILTERS = [10, 11, 12, 16, 18, 255]
@@ -156,6 +157,42 @@ def test_bev_d_empty_future_single_pose(golden):
     g = golden('bev_d')
     out = _bev_case(g, 20, 16, None, (20., 20., 0.5), False)
     _check_bev(out, g, pre=False)
+
+
+@pytest.mark.parametrize('case', EDGE_CASES)
+def test_bev_edges(case):
+    """Hand-built edge inputs run through the real reference: points on cell boundaries and their neighbours, on the crop
+    edge, z at the height filter, even-count medians, cells of exactly 64 values, intensities at the threshold, empty sets."""
+    g = EdgeCase(case)
+    out = _bev_case(g, g.view, g.px, g.hf, g.ints, g.div255, args=(g.rot, g.dx, g.dy, g.zoom))
+    _check_bev(out, g, pre=True)
+
+
+@pytest.mark.parametrize('case', [c for c in EDGE_CASES if c.startswith('lattice_')])
+def test_bev_edges_negative_zero_elevation(case):
+    """Cells whose only z is -0.0.  The reference's rotation (np.matmul: the sum starts from +0.0) hands the elevation
+    map +0.0 there, whatever the signs of x and y, so its fp16 plane holds 0x0000 and never 0x8000; bit for bit the
+    oracle's planes hold the same."""
+    g = EdgeCase(case)
+    out = _bev_case(g, g.view, g.px, g.hf, g.ints, g.div255, args=(g.rot, g.dx, g.dy, g.zoom))
+    names = [str(n) for n in g.file['reserved_names']]
+    for rows in (g['pc_present'], g['pc_future']):
+        neg0 = rows[(rows[:, 2] == 0) & np.signbit(rows[:, 2])]
+        assert neg0.shape[0] == 2                   # the fixture does hold them
+    n_p, n = g['pc_present'].shape[0], out['cells'].shape[0]
+    for s, name in enumerate(orc.SETS):
+        lo, hi = (n_p if s == 1 else 0), (n_p if s == 0 else n)
+        for cell, sets in (('neg0_present', (0, 2)), ('neg0_future', (1, 2)), ('neg0_both', (0, 1, 2))):
+            if s not in sets:
+                continue
+            i, j = g.file['reserved_ij'][names.index(cell)]
+            at = (g.px - 1 - j, i)
+            assert (out['cells'][lo:hi] == at[0] * g.px + at[1]).sum() in (1, 2)    # observed, by these points alone
+            assert g[f'bev_elevation_{name}'].view(np.uint16)[at] == 0x0000
+            assert not np.signbit(g[f'pre_elevation_{name}'][at])
+            assert out['planes'][7 * s + 6].view(np.uint64)[at] == 0
+            assert out['f16'][7 * s + 6].view(np.uint16)[at] == 0x0000
+        assert not (out['f16'][7 * s + 6].view(np.uint16) == 0x8000).any()
 
 
 def test_rgb_bev_medians(golden):

@@ -454,6 +454,396 @@ def case_bev(ref, out_dir):
     print('bev: a,b,c,d,e written')
 
 
+# --------------------------------------------------------------------------
+#  BEV edge fixtures: cell boundaries, crop edges, height filter, medians
+# --------------------------------------------------------------------------
+EDGE_CFGS = {
+    # name: (view, px, height_filter, (int_scaler, int_sep_scaler, int_mid_threshold), intensity_div255)
+    'kitti': (20, 32, None, (20., 20., 0.5), False),
+    'nusc': (51.2, 64, 3., (1., 30., 0.12), True),
+    'px30': (33, 30, 3., (20., 20., 0.5), False),     # not a multiple of the 8 x 8 tile
+    'px7': (10, 7, 1.5, (1., 30., 0.12), True),       # smaller than one tile
+}
+EDGE_ROTS = (0., 0.5 * np.pi, np.pi, 0.7, -2.1)
+EDGE_SHIFTS = ((0., 0., 1.), (1.5, -2.25, 1.1))
+EDGE_CLASSES = (0, 0, 0, 1, 2, 8, 9, 13, 14, 15, 17, 10, 255)   # road / static / dynamic classes / filtered-looking
+
+
+def edge_gen(ref, cfg):
+    view, px, hf, ints, _ = cfg
+    return ref.SemBEVGenerator(SEM_IDXS, view, px, 0., 0., False, *ints, hf)
+
+
+def edge_intensity(rng, n, div255):
+    if div255:
+        return rng.integers(0, 256, n) / 255.
+    return rng.integers(0, 65, n) / 64.               # exact in f32
+
+
+def edge_rows(rng, xy, div255, dyn_frac=0.1):
+    n = xy.shape[0]
+    rows = np.zeros((n, 10))
+    rows[:, :2] = xy
+    rows[:, 2] = rng.integers(-8, 17, n) / 4.         # -2 .. 4 in steps of 0.25 (+0.0 included)
+    rows[:, 3] = edge_intensity(rng, n, div255)
+    rows[:, 4:7] = rng.integers(0, 256, (n, 3))
+    rows[:, 7] = rng.choice(EDGE_CLASSES, n)
+    rows[:, 8] = rng.integers(-1, 4, n)
+    rows[:, 9] = (rng.random(n) < dyn_frac).astype(float)
+    return rows
+
+
+def edge_transformed(gen, rows, rot, dx, dy, aug):
+    """The reference's own geometric_transform output (rotated, shifted, cropped) with the surviving rows' indices."""
+    tagged = np.concatenate([rows, np.arange(rows.shape[0], dtype=float)[:, None]], 1)
+    t = gen.geometric_transform(tagged, rot, dx, dy, aug)
+    return t, t[:, -1].astype(int)
+
+
+def edge_drop_px_hits(gen, rows, rot, dx, dy, aug):
+    """Removes the rows whose grid coordinate floors to px (the reference raises or wraps there)."""
+    px = gen.pixel_size
+    t, idx = edge_transformed(gen, rows, rot, dx, dy, aug)
+    hit = (np.floor(t[:, 0:2] / aug * px + 0.5 * px) == px).any(1)
+    keep = np.ones(rows.shape[0], bool)
+    keep[idx[hit]] = False
+    return rows[keep], int(hit.sum())
+
+
+def edge_check_inputs(gen, rows, rot, dx, dy, aug):
+    """The exclusions every edge fixture keeps: finite coordinates, no grid coordinate == px, no cell with both
+    zeros as z.  Returns (transformed kept rows, their grid coordinates)."""
+    px = gen.pixel_size
+    assert np.isfinite(rows[:, :3]).all()
+    t, _ = edge_transformed(gen, rows, rot, dx, dy, aug)
+    if gen.height_filter is not None:
+        t = t[t[:, 2] < gen.height_filter]
+    t = t[t[:, 9] != 1]
+    ij = np.floor(t[:, 0:2] / aug * px + 0.5 * px)
+    assert not (ij == px).any() and (ij >= 0).all()
+    cell = (ij[:, 1] * px + ij[:, 0]).astype(int)
+    zero = t[:, 2] == 0
+    neg = set(cell[zero & np.signbit(t[:, 2])])
+    pos = set(cell[zero & ~np.signbit(t[:, 2])])
+    assert not (neg & pos), 'a cell holds both +0.0 and -0.0'
+    return t, ij
+
+
+def edge_trajs(view):
+    return bev_inputs(np.random.default_rng(0), 0, 0, 0.45 * view)[1]
+
+
+def edge_write(ref, cfg, pcs_list, out_path, extra=None):
+    """Runs every (present, future, rot, dx, dy, zoom) through generate() and ref_planes(); one npz, keys k<n>_<name>."""
+    view, px, hf, ints, div255 = cfg
+    gen = edge_gen(ref, cfg)
+    trajs = edge_trajs(view)
+    out = dict(n_cases=np.array(len(pcs_list)))
+    for k, (present, future, rot, dx, dy, zoom) in enumerate(pcs_list):
+        aug = zoom * gen.view_size
+        for rows in (present, future, np.concatenate([present, future])):
+            edge_check_inputs(gen, rows, rot, dx, dy, aug)
+        pcs = dict(pc_present=present, pc_future=future, pc_full=np.concatenate([present, future]))
+        one = {}
+        store_inputs(one, pcs, trajs)
+        one['cfg'] = np.array([view, px, np.nan if hf is None else hf, *ints, float(div255), rot, dx, dy, zoom])
+        p, t = copy_inputs(pcs, trajs)
+        flat_bev('bev_', gen.generate(p, t, rot, dx, dy, zoom, True), one)
+        ref_planes(gen, pcs, trajs, one, rot, dx, dy, zoom)
+        del one['pre_grid_rows_present']
+        for key, v in one.items():
+            out[f'k{k}_{key}'] = v
+    for key, v in (extra or {}).items():
+        out[key] = v
+    np.savez_compressed(out_path, **out)
+    assert os.path.getsize(out_path) < 1 << 20, out_path
+    return out
+
+
+def lattice_1d(aug, px):
+    """Cell boundaries (k - px/2) aug/px with both neighbours, cell centres, +-aug/2 with two neighbours each side."""
+    k = np.arange(px + 1)
+    b = (k - 0.5 * px) * aug / px
+    vals = [b, np.nextafter(b, -np.inf), np.nextafter(b, np.inf), (k[:-1] + 0.5 - 0.5 * px) * aug / px]
+    for e in (-0.5 * aug, 0.5 * aug):
+        lo1, hi1 = np.nextafter(e, -np.inf), np.nextafter(e, np.inf)
+        vals.append([e, lo1, hi1, np.nextafter(lo1, -np.inf), np.nextafter(hi1, np.inf)])
+    return np.unique(np.concatenate([np.asarray(v, dtype=float) for v in vals]))
+
+
+def lattice_set(rng, gen, cfg, rot, dx, dy, zoom, which):
+    """One point set on the lattice in VIEW coordinates, taken back through the shift and the rotation."""
+    view, px, hf, ints, div255 = cfg
+    aug = zoom * gen.view_size
+    t1 = lattice_1d(aug, px)
+    if px <= 8:
+        tx, ty = [a.ravel() for a in np.meshgrid(t1, t1)]
+    else:
+        m = -(-500 // t1.size)
+        tx = np.concatenate([np.tile(t1, m), rng.choice(t1, m * t1.size)])
+        ty = np.concatenate([rng.choice(t1, m * t1.size), np.tile(t1, m)])
+    target = np.stack([tx, ty], 1)
+    # reserved cells (grid coordinates i, j) hold hand-made points only
+    reserved = {'neg0_present': (1, 1), 'neg0_future': (3, 2), 'neg0_both': (5, 1), 'min_twice': (2, 4),
+                'only_dyn': (4, 5), 'at_filter': (1, 5), 'below_filter': (5, 4)}
+    ij = np.floor(target / aug * px + 0.5 * px)
+    near = np.zeros(target.shape[0], bool)
+    for ci, cj in reserved.values():                  # keep a margin: a boundary point may land on either side
+        lo = ((np.array([ci, cj]) - 0.5 * px) * aug / px)
+        near |= ((target >= lo - 1e-6) & (target <= lo + aug / px + 1e-6)).all(1)
+    target = target[~near]
+    R = gen.rotation_matrix_3d(rot)[:2, :2]
+    xy = (target - [dx, dy]) @ R                      # R^T (t - d) as row vectors
+    rows = edge_rows(rng, xy, div255)
+    n = rows.shape[0]
+    fz = 3. if hf is None else hf
+    idx = np.arange(n)
+    rows[idx % 7 == 0, 2] = fz
+    rows[idx % 7 == 1, 2] = np.nextafter(fz, -np.inf)
+    # hand-made cells
+    def centre(name):
+        ci, cj = reserved[name]
+        c = (np.array([ci, cj]) + 0.5 - 0.5 * px) * aug / px
+        return (c - [dx, dy]) @ R
+    def point(name, z, sem=0, dyn=0., col=(10, 20, 30), inten=None):
+        r = np.zeros(10)
+        r[:2] = centre(name)
+        r[2] = z
+        r[3] = (51 / 255. if div255 else 0.25) if inten is None else inten
+        r[4:7] = col
+        r[7], r[8], r[9] = sem, -1, dyn
+        return r
+    special = []
+    if which == 'present':
+        special += [point('neg0_present', -0.0), point('neg0_both', -0.0, sem=1)]
+        special += [point('min_twice', -1.5), point('min_twice', 0.25, sem=2), point('min_twice', -1.5, sem=13)]
+    else:
+        special += [point('neg0_future', -0.0, sem=13), point('neg0_both', -0.0)]
+        special += [point('min_twice', -1.5, sem=1)]
+    special += [point('only_dyn', -1.0, dyn=1.), point('only_dyn', 0.5, sem=13, dyn=1.)]
+    special += [point('at_filter', fz), point('below_filter', np.nextafter(fz, -np.inf)), point('below_filter', fz)]
+    rows = np.concatenate([rows, np.array(special)])
+    rows = rows[rng.permutation(rows.shape[0])]
+    rows, n_hit = edge_drop_px_hits(gen, rows, rot, dx, dy, aug)
+    return rows, n_hit, reserved
+
+
+def case_bev_edges(ref, out_dir):
+    """Hand-built edge inputs through the real reference: tests/golden/bev_edges_<name>.npz (see tools/README.md)."""
+    # ---- lattice: one file per parameter set, rotations x shifts inside ----
+    for c, (cname, cfg) in enumerate(EDGE_CFGS.items()):
+        view, px, hf, ints, div255 = cfg
+        gen = edge_gen(ref, cfg)
+        rng = np.random.default_rng(700 + c)
+        for r, rot in enumerate(EDGE_ROTS):           # one file per rotation, the shifts inside
+            cases, stats = [], []
+            for dx, dy, zoom in EDGE_SHIFTS:
+                aug = zoom * gen.view_size
+                present, hit_p, reserved = lattice_set(rng, gen, cfg, rot, dx, dy, zoom, 'present')
+                future, hit_f, _ = lattice_set(rng, gen, cfg, rot, dx, dy, zoom, 'future')
+                full = np.concatenate([present, future])
+                t, _ = edge_transformed(gen, full, rot, dx, dy, aug)
+                n_in, n_out = t.shape[0], full.shape[0] - t.shape[0]
+                fz = 3. if hf is None else hf
+                n_at, n_below = int((t[:, 2] == fz).sum()), int((t[:, 2] == np.nextafter(fz, -np.inf)).sum())
+                s = t[:, 0:2] / aug * px + 0.5 * px
+                n_exact = int((s == np.floor(s)).any(1).sum())
+                # many points on each side of the crop and of the height filter, or the fixture has degenerated
+                assert n_in > 200 and n_out > 40, (cname, rot, n_in, n_out)
+                assert n_at > 40 and n_below > 40, (cname, rot, n_at, n_below)
+                if rot == 0. and dx == 0.:
+                    assert n_exact > 100, (cname, n_exact)         # exact arithmetic: points ON cell boundaries
+                stats.append((n_in, n_out, n_exact, hit_p + hit_f))
+                cases.append((present, future, rot, dx, dy, zoom))
+            res = np.array([[i, j] for i, j in reserved.values()])
+            edge_write(ref, cfg, cases, os.path.join(out_dir, f'bev_edges_lattice_{cname}_r{r}.npz'),
+                       dict(reserved_names=np.array(list(reserved)), reserved_ij=res))
+            print(f'bev_edges lattice_{cname}_r{r}: (in view, cropped, on a boundary, dropped at px) per case', stats)
+    case_bev_edges_counts(ref, out_dir)
+    case_bev_edges_intensity(ref, out_dir)
+    case_bev_edges_empty(ref, out_dir)
+
+
+def centre_xy(i, j, view, px):
+    return np.array([(i + 0.5 - 0.5 * px) * view / px, (j + 0.5 - 0.5 * px) * view / px])
+
+
+COUNTS_CFG = (32, 64, None, (1., 30., 0.12), True)    # cell 0.5 m, tile 4 m: every centre is exact
+
+
+def counts_cell(rng, i, j, n, scheme, sem='mixed', dyn=0., div255=True):
+    """n points at the centre of cell (i, j); colours take two values only.  scheme: per channel how many get the low
+    value -- 'half' (even n: an x.5 median), 'all' (all equal), 'mid' (the two middle values equal)."""
+    view, px = COUNTS_CFG[:2]
+    rows = np.zeros((n, 10))
+    rows[:, :2] = centre_xy(i, j, view, px)
+    rows[:, 2] = rng.integers(-8, 17, n) / 4.
+    rows[:, 3] = edge_intensity(rng, n, div255)
+    lo, hi = (10, 60, 200), (201, 61, 255)
+    for ch, how in enumerate(scheme):
+        n_lo = {'half': n // 2, 'all': n, 'mid': min(n, n // 2 + 1), 'none': 0}[how]
+        col = np.full(n, hi[ch], dtype=float)
+        col[:n_lo] = lo[ch]
+        rows[:, 4 + ch] = rng.permutation(col)
+    if sem == 'mixed':
+        rows[:, 7] = rng.choice([0, 0, 1, 2, 13, 17], n)
+    else:
+        rows[:, 7] = sem
+    rows[:, 8] = -1
+    rows[:, 9] = dyn
+    return rows
+
+
+def case_bev_edges_counts(ref, out_dir):
+    cfg = COUNTS_CFG
+    view, px = cfg[:2]
+    gen = edge_gen(ref, cfg)
+    rng = np.random.default_rng(811)
+    present, future = [], []
+    table = []                                        # (i, j, n_present, n_future)
+    schemes = (('half', 'all', 'mid'), ('mid', 'half', 'all'), ('all', 'mid', 'half'))
+    counts = (1, 2, 3, 4, 63, 64, 65, 66, 128)
+    for k, n in enumerate(counts):
+        for v, sch in enumerate(schemes):             # rows j = 2 + v (present only), 6 + v (future only)
+            present.append(counts_cell(rng, 2 + 2 * k, 2 + v, n, sch))
+            table.append((2 + 2 * k, 2 + v, n, 0))
+            future.append(counts_cell(rng, 2 + 2 * k, 6 + v, n, sch))
+            table.append((2 + 2 * k, 6 + v, 0, n))
+    # 'full' crossing 64 with neither set above it, and landing exactly on the counts again
+    for k, (n_p, n_f) in enumerate(((32, 32), (63, 1), (1, 63), (33, 32), (40, 26), (64, 64), (64, 1), (2, 2), (1, 1),
+                                    (1, 2), (63, 65), (60, 3))):
+        sch = schemes[k % 3]
+        present.append(counts_cell(rng, 2 + 2 * k, 12, n_p, sch))
+        future.append(counts_cell(rng, 2 + 2 * k, 12, n_f, sch))
+        table.append((2 + 2 * k, 12, n_p, n_f))
+    # one class only / dynamic only (the static partition leaves the last cell empty)
+    for k, (sem, dyn) in enumerate(((0, 0.), (1, 0.), (13, 0.), (0, 1.), (13, 1.))):
+        for v, n in enumerate((1, 2, 64, 65)):
+            present.append(counts_cell(rng, 30 + 2 * k, 16 + 2 * v, n, schemes[v % 3], sem, dyn))
+            future.append(counts_cell(rng, 30 + 2 * k, 16 + 2 * v, n + 1, schemes[v % 3], sem, dyn))
+            table.append((30 + 2 * k, 16 + 2 * v, n if not dyn else 0, n + 1 if not dyn else 0))
+    # a tile with more colour records than stay resident (batches; heavy kernel): grid columns 32..39, rows j 32..39;
+    # and a heavy tile that still fits (columns 40..47).  One cell of each holds exactly 64 / 63 + 1 values.
+    for i0, per_p, per_f in ((32, 60, 45), (40, 30, 22)):
+        for ci in range(8):
+            for cj in range(8):
+                n_p, n_f = per_p + (ci * 8 + cj) % 5, per_f + (ci + cj) % 3
+                if (ci, cj) == (3, 4):
+                    n_p, n_f = 64, 0
+                if (ci, cj) == (4, 3):
+                    n_p, n_f = 63, 1
+                if (ci, cj) == (0, 7):
+                    n_p, n_f = 0, 64
+                sch = schemes[(ci + cj) % 3]
+                if n_p:
+                    present.append(counts_cell(rng, i0 + ci, 32 + cj, n_p, sch))
+                if n_f:
+                    future.append(counts_cell(rng, i0 + ci, 32 + cj, n_f, sch))
+                table.append((i0 + ci, 32 + cj, n_p, n_f))
+    present, future = np.concatenate(present), np.concatenate(future)
+    # points outside the view (identical rows): the window is larger than what level 1 keeps in registers when it
+    # runs as one piece
+    far = np.zeros((18000 - present.shape[0] - future.shape[0], 10))
+    far[:, 0], far[:, 3], far[:, 8] = 1000., 1., -1
+    assert far.shape[0] > 0
+    present = np.concatenate([present, far[:far.shape[0] // 2]])
+    future = np.concatenate([future, far[far.shape[0] // 2:]])
+    present = present[rng.permutation(present.shape[0])]
+    future = future[rng.permutation(future.shape[0])]
+    table = np.array(table)
+    # the table is what the reference sees: static points per cell and set
+    for rows, col in ((present, 2), (future, 3)):
+        t, ij = edge_check_inputs(gen, rows, 0., 0., 0., float(view))
+        got = np.bincount((ij[:, 1] * px + ij[:, 0]).astype(int), minlength=px * px)
+        want = np.zeros(px * px, int)
+        want[table[:, 1] * px + table[:, 0]] = table[:, col]
+        assert np.array_equal(got, want)
+    tile_records = [(table[(table[:, 0] // 8 == a) & (table[:, 1] // 8 == 4), 2:].sum()) for a in (4, 5)]
+    assert tile_records[0] > 4096 and 2560 < tile_records[1] <= 4096, tile_records
+    edge_write(ref, cfg, [(present, future, 0., 0., 0., 1.)], os.path.join(out_dir, 'bev_edges_counts.npz'),
+               dict(cell_counts=table))
+    print('bev_edges counts:', present.shape[0], '+', future.shape[0], 'points, dense tiles hold', tile_records)
+
+
+def case_bev_edges_intensity(ref, out_dir):
+    """Road cells whose mean intensity sum / (count + 1) sits at and around int_mid_threshold, at 0 and at the largest
+    raw value, for counts 1 .. 255; both parameter triples of the drivers."""
+    rng = np.random.default_rng(822)
+    for cname in ('kitti', 'nusc'):
+        cfg = EDGE_CFGS[cname]
+        view, px, hf, ints, div255 = cfg
+        gen = edge_gen(ref, cfg)
+        thr = ints[2]
+        sets = {'present': [], 'future': []}
+        cell = 0
+        for n in (1, 2, 3, 9, 50, 255):
+            want = thr * (n + 1) / n                  # n v / (n + 1) == thr
+            if div255:
+                k0 = int(np.floor(want * 255.))
+                vals = [0., 1.] + [k / 255. for k in range(max(k0 - 2, 0), min(k0 + 4, 256))]
+            else:
+                w32 = np.float32(min(want, 1.))
+                vals = [0., 1., float(w32), float(np.nextafter(w32, np.float32(0))),
+                        float(np.nextafter(w32, np.float32(2))), float(np.float32(0.9) * w32), float(np.float32(thr))]
+            for v in vals:
+                for which in ('present', 'future'):
+                    i, j = 1 + cell % (px - 2), 1 + cell // (px - 2)
+                    cell += 1
+                    rows = np.zeros((n, 10))
+                    rows[:, :2] = centre_xy(i, j, view, px)
+                    rows[:, 2] = rng.integers(-8, 11, n) / 4.
+                    rows[:, 3] = v
+                    rows[:, 4:7] = rng.integers(0, 256, (n, 3))
+                    rows[:, 8] = -1
+                    sets[which].append(rows)
+                    if n == 3:                        # non-road and dynamic points in the cell change nothing
+                        other = rows.copy()
+                        other[:, 7], other[:, 3] = 2, 1.
+                        other[0, 7], other[0, 9] = 0, 1.
+                        sets[which].append(other)
+            # mixed values in one cell, seen by both sets: the sum is taken in point order
+            for which in ('present', 'future'):
+                i, j = 1 + cell % (px - 2), 1 + cell // (px - 2)
+                rows = np.zeros((n, 10))
+                rows[:, :2] = centre_xy(i, j, view, px)
+                rows[:, 3] = edge_intensity(rng, n, div255)
+                rows[:, 4:7] = rng.integers(0, 256, (n, 3))
+                rows[:, 8] = -1
+                sets[which].append(rows)
+            cell += 1
+        assert 1 + cell // (px - 2) < px - 1
+        present, future = (np.concatenate(sets[w]) for w in ('present', 'future'))
+        present = present[rng.permutation(present.shape[0])]
+        future = future[rng.permutation(future.shape[0])]
+        out = edge_write(ref, cfg, [(present, future, 0., 0., 0., 1.)],
+                         os.path.join(out_dir, f'bev_edges_intensity_{cname}.npz'))
+        raw = out['k0_pre_intraw_present']
+        assert (raw == 0).sum() > 0 and (raw > thr).sum() > 5 and ((raw < thr) & (raw > 0)).sum() > 5
+        print(f'bev_edges intensity_{cname}:', present.shape[0], '+', future.shape[0], 'points; cells at the threshold:',
+              int((raw == thr).sum()))
+
+
+def case_bev_edges_empty(ref, out_dir):
+    """Present empty with future populated, the reverse, and every point outside the view by one ulp."""
+    cfg = EDGE_CFGS['nusc']
+    view, px, hf, ints, div255 = cfg
+    rng = np.random.default_rng(833)
+    some = edge_rows(rng, rng.integers(-200, 201, (600, 2)) / 8., div255)
+    empty = np.zeros((0, 10))
+    e = 0.5 * view
+    out1 = [np.nextafter(e, np.inf), e, -e, np.nextafter(-e, -np.inf)]
+    xy = [(a, b) for a in out1 for b in (0.4, -25.6, 25.5, e)] + [(b, a) for a in out1 for b in (0.4, -25.6, 25.5, -e)]
+    outside = edge_rows(rng, np.array(xy), div255, dyn_frac=0.)
+    inside_but_high = edge_rows(rng, rng.integers(-200, 201, (40, 2)) / 8., div255, dyn_frac=0.)
+    inside_but_high[:, 2] = hf                        # z == height_filter: dropped
+    gone = np.concatenate([outside, inside_but_high])
+    cases = [(empty, some, 0., 0., 0., 1.), (some, empty, 0., 0., 0., 1.), (gone[:40], gone[40:], 0., 0., 0., 1.)]
+    out = edge_write(ref, cfg, cases, os.path.join(out_dir, 'bev_edges_empty_sets.npz'))
+    assert int(out['k2_pre_n_grid_full']) == 0 and int(out['k0_pre_n_grid_present']) == 0
+    assert int(out['k0_pre_n_grid_future']) > 300 and int(out['k1_pre_n_grid_future']) == 0
+    print('bev_edges empty_sets written')
+
+
 def case_nusc(ref, out_dir):
     from PIL import Image
     rng = np.random.default_rng(404)
@@ -671,7 +1061,8 @@ def main():
     np.random.seed(0)
     ref = import_reference()
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
-                 nusc=case_nusc, utils=case_utils, sweeps=case_sweeps)
+                 bev_edges=case_bev_edges, nusc=case_nusc, utils=case_utils,
+                 sweeps=case_sweeps)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
