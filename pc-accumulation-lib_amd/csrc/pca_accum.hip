@@ -758,18 +758,6 @@ int pca_nusc_sample_filter_transform_ex(pca_ctx *ctx, const double *pc, const in
     return 0;
 }
 
-static int accum_grow(pca_ctx *ctx, void **p, int64_t *cap, int64_t need, hipStream_t s)
-{
-    if (need <= *cap) return 0;
-    PCA_CHECK(ctx, hipStreamSynchronize(s));
-    if (*p) PCA_CHECK(ctx, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const int64_t want = need + need / 4;
-    PCA_CHECK(ctx, hipMalloc(p, (size_t)want));
-    *cap = want;
-    return 0;
-}
-
 #define K1N_MAX_BATCH_TILES 16384       // k1n_append_batch adds up the counts before its tile
 int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *frames, int n_frames, int ncam, int H, int W,
                                            const uint64_t filter_mask[4], const pca_store *store, int64_t *frame_off,
@@ -793,7 +781,7 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     // descriptors + tile -> frame table: built in pinned memory, one asynchronous upload
-    const int64_t desc_bytes = (((int64_t)sizeof(K1nFrame) * n_frames + 255) & ~255ll), table_bytes = ((total * 4 + 255) & ~255ll);
+    const int64_t desc_bytes = pca_align256((int64_t)sizeof(K1nFrame) * n_frames), table_bytes = pca_align256(total * 4);
     const int64_t up_bytes = desc_bytes + table_bytes;
     if (ctx->k1n_busy) { PCA_CHECK(ctx, hipEventSynchronize(ctx->k1n_ev)); ctx->k1n_busy = false; }
     if (up_bytes > ctx->k1n_pin_cap) {
@@ -803,7 +791,7 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
         ctx->k1n_pin_cap = 2 * up_bytes;
     }
     if (!ctx->k1n_ev) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->k1n_ev, hipEventDisableTiming));
-    if (accum_grow(ctx, &ctx->k1n_desc_dev, &ctx->k1n_desc_cap, up_bytes, s)) return -1;
+    if (pca_dev_grow(ctx, &ctx->k1n_desc_dev, &ctx->k1n_desc_cap, up_bytes, s)) return -1;
     K1nFrame *hf = reinterpret_cast<K1nFrame *>(ctx->k1n_pin);
     int32_t *ht = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(ctx->k1n_pin) + desc_bytes);
     int32_t tile0 = 0;
@@ -818,8 +806,8 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
     }
     // staging: sx sy sz f64 | si f32 | sc u32 | sn i32 | counts u32 | lastf i32
     const int64_t slots = total * TILE_PTS;
-    const int64_t need = 3 * slots * 8 + 3 * slots * 4 + 2 * ((total * 4 + 255) & ~255ll) + 1024;
-    if (accum_grow(ctx, &ctx->k1n_ws, &ctx->k1n_ws_cap, need, s)) return -1;
+    const int64_t need = 3 * slots * 8 + 3 * slots * 4 + 2 * pca_align256(total * 4) + 1024;
+    if (pca_dev_grow(ctx, &ctx->k1n_ws, &ctx->k1n_ws_cap, need, s)) return -1;
     if (ctx->profiling == 1) pca_prof_begin(ctx, PCA_K_NUSC, s);
     // (descriptors + tile table, ~20 KB: fetched by a kernel from the mapped host block -- a copy command of this size was
     // 13-17 us of a 60-95 us call; PCA_SMALL_COPY=1 restores it for A/B)
@@ -840,7 +828,7 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
     a.si = reinterpret_cast<float *>(w); w += slots * 4;
     a.sc = reinterpret_cast<uint32_t *>(w); w += slots * 4;
     a.sn = reinterpret_cast<int32_t *>(w); w += slots * 4;
-    a.counts = reinterpret_cast<uint32_t *>(w); w += (total * 4 + 255) & ~255ll;
+    a.counts = reinterpret_cast<uint32_t *>(w); w += pca_align256(total * 4);
     a.lastf = reinterpret_cast<int32_t *>(w);
     a.st = *store; a.frame_off = frame_off; a.first_slot = first_slot;
     a.status = ctx->ticket + 1;
@@ -976,7 +964,6 @@ int pca_mark_dynamic(pca_ctx *ctx, const pca_store *store, const int64_t *frame_
 }
 
 
-static inline int64_t dd_align(int64_t v) { return (v + 255) & ~255ll; }
 static inline int64_t dedup_capacity(int64_t max_points)
 {
     int64_t cap = 1024;
@@ -988,7 +975,7 @@ int64_t pca_voxel_dedup_workspace_bytes(int64_t max_points, int n_slots)
 {
     if (max_points < 1) max_points = 1;
     const int64_t cap = dedup_capacity(max_points);
-    return dd_align(cap * 8) + dd_align(cap * 4) + dd_align((int64_t)(n_slots + 2) * 8) + 512;
+    return pca_align256(cap * 8) + pca_align256(cap * 4) + pca_align256((int64_t)(n_slots + 2) * 8) + 512;
 }
 
 int pca_voxel_dedup(pca_ctx *ctx, const pca_store *store, int64_t *frame_off, int slot_begin, int slot_end,
@@ -1011,9 +998,9 @@ int pca_voxel_dedup(pca_ctx *ctx, const pca_store *store, int64_t *frame_off, in
     a.max_points = max_points;
     a.size = voxel_size;
     const int64_t cap = dedup_capacity(max_points);
-    char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    a.keys = reinterpret_cast<unsigned long long *>(w); w += dd_align(cap * 8);
-    a.vals = reinterpret_cast<uint32_t *>(w); w += dd_align(cap * 4);
+    char *w = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
+    a.keys = reinterpret_cast<unsigned long long *>(w); w += pca_align256(cap * 8);
+    a.vals = reinterpret_cast<uint32_t *>(w); w += pca_align256(cap * 4);
     a.new_off = reinterpret_cast<int64_t *>(w);
     a.cap_mask = (uint64_t)cap - 1;
     constexpr int BLK = 256;

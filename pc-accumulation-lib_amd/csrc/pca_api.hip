@@ -22,6 +22,18 @@ int pca_fetch_block(pca_ctx *ctx, const void *mapped_host, int64_t offset, void 
     return 0;
 }
 
+int pca_dev_grow(pca_ctx *ctx, void **p, int64_t *cap, int64_t need, hipStream_t s)
+{
+    if (need <= *cap) return 0;
+    PCA_CHECK(ctx, hipStreamSynchronize(s));
+    if (*p) PCA_CHECK(ctx, hipFree(*p));
+    *p = nullptr; *cap = 0;
+    const int64_t want = need + need / 4;
+    PCA_CHECK(ctx, hipMalloc(p, (size_t)want));
+    *cap = want;
+    return 0;
+}
+
 int pca_ctx_reserve_tiles(pca_ctx *ctx, int64_t tiles, hipStream_t s)
 {
     if (tiles <= ctx->tile_cap) return 0;
@@ -305,8 +317,8 @@ void pca_ctx_destroy(pca_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->tile_state) (void)hipFree(ctx->tile_state);
     if (ctx->ticket) (void)hipFree(ctx->ticket);
+    if (ctx->k1_ws) (void)hipFree(ctx->k1_ws);
     for (int i = 0; i < 2; ++i) {
-        if (ctx->k1_ws[i]) (void)hipFree(ctx->k1_ws[i]);
         if (ctx->k1_pin[i]) (void)hipHostFree(ctx->k1_pin[i]);
         if (ctx->k1_pin_ev[i]) (void)hipEventDestroy(ctx->k1_pin_ev[i]);
     }

@@ -1720,7 +1720,6 @@ __global__ __launch_bounds__(H_THREADS) void bev_tile_cells_heavy_band_many()
 // ---------------------------------------------------------------------------------------------
 int pca_k1_prepare_pending(pca_ctx *ctx, K1Args *out, int *n_tiles, hipStream_t s);    // pca_k1.hip
 void pca_k1_pending_launched(pca_ctx *ctx, hipStream_t s);
-static inline int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
 static inline int tiles_x(int px) { return (px + TS - 1) / TS; }
 // Banded rasters.  Level 1 keeps a histogram entry and a cursor per tile in LDS (8 B): 128 KiB for the 16 384 tiles of a
 // 1024^2 grid.  Larger grids (up to 4096^2) run as bands of whole tile rows of at most BAND_TILES tiles each, one level-1 pass
@@ -1766,14 +1765,14 @@ static BevLayout bev_layout(int64_t max_points, int px)
 {
     if (max_points < 1) max_points = 1;
     const int64_t T = (int64_t)band_rows(px) * tiles_x(px), G = n_groups(max_points);
-    const int64_t table = align256((G + K1_RIDE + 8) * T * 4);                 // bh, boff, bh0: one each
+    const int64_t table = pca_align256((G + K1_RIDE + 8) * T * 4);                 // bh, boff, bh0: one each
     BevLayout l;
     l.T = (int)T; l.G = (int)G;
-    l.bh = align256(max_points * 4);
+    l.bh = pca_align256(max_points * 4);
     l.boff = l.bh + table; l.bh0 = l.boff + table;
     l.heavy = l.bh0 + table;
-    l.recs = l.heavy + align256((HQ_IDS + HQ_CLASSES * T) * 4);
-    l.total = l.recs + align256((max_points + G + K1_RIDE + K1_SEG) * 24) + 512;
+    l.recs = l.heavy + pca_align256((HQ_IDS + HQ_CLASSES * T) * 4);
+    l.total = l.recs + pca_align256((max_points + G + K1_RIDE + K1_SEG) * 24) + 512;
     return l;
 }
 
@@ -1875,7 +1874,7 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     a.T = l.T;                                              // (the workspace's layout: the largest band)
     a.G = l.G;
     bev_table_order(a);
-    char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char *w = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
     a.key = reinterpret_cast<uint32_t *>(w);
     a.bh = reinterpret_cast<uint32_t *>(w + l.bh);
     a.boff = reinterpret_cast<uint32_t *>(w + l.boff);
@@ -2111,7 +2110,7 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
     }
     if (!ctx->bevm_ev) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->bevm_ev, hipEventDisableTiming));
     BevArgs *ha = reinterpret_cast<BevArgs *>(ctx->bevm_pin);
-    char *ws = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char *ws = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
     for (int k = 0; k < n_jobs; ++k) {
         const pca_bev_job &j = jobs[k];
         if (j.prm.px != px) { ctx->err = "bev: the rasters of one call share the grid size"; return -1; }

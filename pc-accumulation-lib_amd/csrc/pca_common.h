@@ -67,8 +67,8 @@ struct pca_ctx {
     uint32_t stage_next = 0;
     void *k1_tiny = nullptr;          // dev: 4-byte copies of images smaller than the 4-byte colour gather
     int64_t k1_tiny_cap = 0;
-    void *k1_ws[2] = {nullptr, nullptr};   // dev: counts / kept records of K1's split form, one per sub-batch in flight
-    int64_t k1_ws_cap[2] = {0, 0};         // bytes
+    void *k1_ws = nullptr;            // dev: counts / kept records of K1's split form (k1_ws_layout), shared by a call's sub-batches
+    int64_t k1_ws_cap = 0;            // bytes
     K1Frame *k1_pin[2] = {nullptr, nullptr};   // pinned staging of the descriptors, alternating between calls
     int k1_pin_cap[2] = {0, 0};
     hipEvent_t k1_pin_ev[2] = {nullptr, nullptr};
@@ -148,12 +148,19 @@ static inline int64_t pca_env_int(const char *name, int64_t dflt, int64_t lo = I
     return (v < lo || v > hi) ? dflt : v;
 }
 #define PCA_ENV_ONCE(...) ([]() -> int64_t { static const int64_t v = pca_env_int(__VA_ARGS__); return v; }())
+// (the two switches whose value is a word -- PCA_K1_MODE=split, PCA_K1_APPEND=<n>,nt: the variable's text, "" when unset)
+static inline const char *pca_env_str(const char *name) { const char *e = getenv(name); return e ? e : ""; }
 static inline bool pca_small_copy() { return PCA_ENV_ONCE("PCA_SMALL_COPY", 0) != 0; }   // 1: small argument blocks by a copy command (A/B)
 
 // internal (pca_k1.hip): runs a deferred K1 now, on its own (no-op without one).  Every entry point that reads or writes a
 // store, frame_off or the status word calls it first.
 int pca_k1_flush_pending(pca_ctx *ctx);
 // internal (pca_api.hip)
+// The regions of every workspace start on 256-byte boundaries.
+static inline int64_t pca_align256(int64_t v) { return (v + 255) & ~255ll; }
+// A device buffer the context owns, grown to at least `need` bytes (a quarter more, so that a slowly growing demand does not
+// reallocate every call; the old contents are NOT kept).  Growing waits for the stream first: rare, the first calls only.
+int pca_dev_grow(pca_ctx *ctx, void **p, int64_t *cap, int64_t need, hipStream_t s);
 // Small argument blocks (frame descriptors, raster parameters: a few KB) from MAPPED host memory into device memory by a
 // KERNEL that reads the host block over PCIe: a copy command of that size costs 13-17 us on this stack (measured as the gap
 // between the HIP-event time of a batched K1n call and the sum of its kernels), a launch 2-3.  `mapped_host`: from

@@ -1090,16 +1090,15 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_init(const IcpArgs a, const I
 
 extern "C" {
 
-static inline int64_t icp_align(int64_t v) { return (v + 255) & ~255ll; }
 static inline int icp_grid(int n, int sg = 16) { const int qpw = ICP_THREADS / sg; return (n + qpw - 1) / qpw; }   // workgroups of icp_match = columns of partial sums
 
 int64_t pca_icp_workspace_bytes(int32_t max_points)
 {
     if (max_points < 1) max_points = 1;
-    return 2 * (icp_align(ICP_CELLS * 4) + icp_align((ICP_CELLS + 1) * 4) + icp_align((int64_t)max_points * 16)) +
-           icp_align((int64_t)max_points * 16) + 3 * icp_align((int64_t)max_points * 4) +
-           icp_align((int64_t)icp_grid(max_points) * ICP_NACC * 8) + icp_align((int64_t)((max_points + ICP_THREADS - 1) / ICP_THREADS) * 16) +
-           icp_align(128 * 8) + 512;
+    return 2 * (pca_align256(ICP_CELLS * 4) + pca_align256((ICP_CELLS + 1) * 4) + pca_align256((int64_t)max_points * 16)) +
+           pca_align256((int64_t)max_points * 16) + 3 * pca_align256((int64_t)max_points * 4) +
+           pca_align256((int64_t)icp_grid(max_points) * ICP_NACC * 8) + pca_align256((int64_t)((max_points + ICP_THREADS - 1) / ICP_THREADS) * 16) +
+           pca_align256(128 * 8) + 512;
 }
 
 int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const float *tgt_pts, int32_t n_tgt,
@@ -1115,7 +1114,7 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     IcpArgs a;
     a.src = src_pts; a.tgt = tgt_pts; a.n_src = n_src; a.n_tgt = n_tgt;
-    char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char *w = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
     const int64_t cells = (int64_t)ICP_NX * ICP_NY * ICP_NZ;
     // the count tables belong to the context: the fill pass leaves them all zero, so only a first use (or a call that
     // failed half way) clears them -- 2 x 67 MB of memset per registration otherwise
@@ -1131,19 +1130,19 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     if (ctx->icp_cnt_dirty) PCA_CHECK(ctx, hipMemsetAsync(ctx->icp_cnt, 0, (size_t)(2 * cells * 4), s));
     ctx->icp_cnt_dirty = true;                              // until this call has come through
     for (int lv = 0; lv < 2; ++lv) {
-        a.g[lv].cnt = ctx->icp_cnt + (size_t)lv * cells; w += icp_align(cells * 4);      // (the workspace's own slot stays unused)
-        a.g[lv].start = reinterpret_cast<uint32_t *>(w); w += icp_align((cells + 1) * 4);
-        a.g[lv].spts = reinterpret_cast<float4 *>(w); w += icp_align((int64_t)n_tgt * 16);
+        a.g[lv].cnt = ctx->icp_cnt + (size_t)lv * cells; w += pca_align256(cells * 4);      // (the workspace's own slot stays unused)
+        a.g[lv].start = reinterpret_cast<uint32_t *>(w); w += pca_align256((cells + 1) * 4);
+        a.g[lv].spts = reinterpret_cast<float4 *>(w); w += pca_align256((int64_t)n_tgt * 16);
     }
-    a.normal = reinterpret_cast<float *>(w); w += icp_align((int64_t)n_tgt * 16);
-    a.nn_prev = reinterpret_cast<int32_t *>(w); w += icp_align((int64_t)n_src * 4);
-    a.nn_cell = reinterpret_cast<int32_t *>(w); w += icp_align((int64_t)n_src * 4);
-    a.nn_slack = reinterpret_cast<float *>(w); w += icp_align((int64_t)n_src * 4);
+    a.normal = reinterpret_cast<float *>(w); w += pca_align256((int64_t)n_tgt * 16);
+    a.nn_prev = reinterpret_cast<int32_t *>(w); w += pca_align256((int64_t)n_src * 4);
+    a.nn_cell = reinterpret_cast<int32_t *>(w); w += pca_align256((int64_t)n_src * 4);
+    a.nn_slack = reinterpret_cast<float *>(w); w += pca_align256((int64_t)n_src * 4);
     a.no_skip = (int)PCA_ENV_ONCE("PCA_ICP_NO_SKIP", 0);
     a.dbg = (int)PCA_ENV_ONCE("PCA_ICP_DBG", 0);
-    a.partial = reinterpret_cast<double *>(w); w += icp_align((int64_t)icp_grid(n_src) * ICP_NACC * 8);
+    a.partial = reinterpret_cast<double *>(w); w += pca_align256((int64_t)icp_grid(n_src) * ICP_NACC * 8);
     a.n_count_blocks = (n_tgt + ICP_THREADS - 1) / ICP_THREADS;
-    a.zr_part = reinterpret_cast<uint32_t *>(w); w += icp_align((int64_t)a.n_count_blocks * 16);
+    a.zr_part = reinterpret_cast<uint32_t *>(w); w += pca_align256((int64_t)a.n_count_blocks * 16);
     a.state = reinterpret_cast<double *>(w);
     a.zr = reinterpret_cast<uint32_t *>(a.state + 24);                 // initialised with the state block
     a.status = ctx->ticket + 1;

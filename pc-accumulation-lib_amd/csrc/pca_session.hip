@@ -11,8 +11,6 @@
 
 int pca_stage_copy(const void *const *src, void *const *dst, const int64_t *bytes, int n);      // pca_host.hip
 
-static inline int64_t up256(int64_t v) { return (v + 255) & ~255ll; }
-
 extern "C" {
 
 // integrate() of one KITTI-360 observation (kitti360_sem_pc_accum.py:41-88 of the reference, per-point work = K1):
@@ -36,7 +34,7 @@ int pca_kitti_integrate(pca_ctx *ctx, const pca_kitti_obs *obs, const double P[1
     int64_t off[4] = {0, 0, 0, 0}, total = 0;
     for (int k = 0; k < 4; ++k) {
         if (!(in[k] && ((obs->host_mask >> k) & 1u))) continue;
-        if (size[k] > 0) { off[k] = total; total += up256(size[k]); }
+        if (size[k] > 0) { off[k] = total; total += pca_align256(size[k]); }
         else dev[k] = nullptr;                             // an empty host array: nothing to stage, nothing the device may touch
     }
     pca_ctx::Stage *slot_st = nullptr;

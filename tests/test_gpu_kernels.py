@@ -950,6 +950,93 @@ def test_k1_one_pixel_image(T, orc):
         assert ost.n > 10 and np.array_equal(rows, ost.rows())
 
 
+# K1's host paths: the sub-batch cut, uploaded descriptors, the per-call switches
+P_PLUS_X = np.array([[40., 0, 48, 0], [0, 40., 32, 0], [0, 0, 1, 0]]) @ np.array(
+    [[0., -1, 0, 0], [0, 0, -1, 0], [1, 0, 0, 0], [0, 0, 0, 1]])      # the camera of test_k1_defer_semantics_at_the_c_abi: along +x
+
+
+def test_k1_sub_batch_cut_two_plans_share_one_workspace(T, orc):
+    """One call of 16 384 + 16 one-tile frames: the split form cuts it into a plan of 16 384 frames (descriptors uploaded) and
+    one of 16 equal frames (descriptors inline) that run one after the other over the same workspace; the second plan's
+    slots, host and device descriptors start 16 384 frames in.  Rows and segment sizes against the oracle."""
+    rng = np.random.default_rng(11)
+    H, W, n_frames = 8, 12, 16384 + 16
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    sem = rng.integers(0, 19, (H, W)).astype(np.uint8)
+    pool = []
+    for j in range(7):                                     # 1..5 points, about half of them inside the 12 x 8 image
+        n = 1 + j % 5
+        x = rng.uniform(2, 10, n)
+        inside = rng.random(n) < 0.45
+        y = x * np.where(inside, rng.uniform(0.93, 1.19, n), rng.uniform(-1.0, 0.5, n))
+        z = x * rng.uniform(0.63, 0.79, n)
+        pool.append(np.stack([x, y, z, rng.uniform(0, 1, n)], 1).astype(np.float32))
+    d_img, d_sem, d_pool = cu(T, img), cu(T, sem), [cu(T, pc) for pc in pool]
+    order = [(k * 3 + k // 7) % 7 for k in range(n_frames)]
+    ost = orc.Store(n_frames * 5)
+    sizes = [orc.kitti_project_sample_filter(ost, pool[j], P_PLUS_X, img, sem, None, H, W, KITTI_FILTERS) for j in order]
+    n_in = sum(len(pool[j]) for j in order)
+    assert n_in // 4 < ost.n < 3 * n_in // 4 and len(set(sizes)) > 2      # (the oracle's own count: not an empty store)
+    st = dev_store(capacity=1 << 17, max_frames=32768)
+    st.append_kitti([dict(pts=d_pool[j], rgb=d_img, sem=d_sem) for j in order], P_PLUS_X, H, W, KITTI_FILTERS)
+    st.check_status()
+    assert st.sizes().tolist() == sizes
+    assert np.array_equal(st.rows(), ost.rows())
+
+
+def test_k1_uploaded_descriptors_with_equal_frames(T, orc, monkeypatch):
+    """70 frames x 2 049 points in the split form: two 512 x 4 tiles per frame (the closed-form tile -> frame index), too many
+    frames for inline descriptors, eight queues of 9 or 8 frames (70 = 8 x 8 + 6).  (Forced: 70 x 3 tiles of the fused form's
+    1024 points would still fit a 256-CU device.)"""
+    monkeypatch.setenv('PCA_K1_MODE', 'split')
+    rng = np.random.default_rng(12)
+    H, W = 64, 96
+    st = dev_store(capacity=70 * 2049, max_frames=128)
+    ost = orc.Store(70 * 2049)
+    frames, sizes = [], []
+    for _ in range(70):
+        pc = np.stack([rng.uniform(0.5, 20, 2049), rng.uniform(-9, 9, 2049), rng.uniform(-1, 2, 2049), rng.uniform(0, 1, 2049)],
+                      1).astype(np.float32)
+        img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        sem = rng.integers(0, 19, (H, W)).astype(np.uint8)
+        frames.append(dict(pts=cu(T, pc), rgb=cu(T, img), sem=cu(T, sem)))
+        sizes.append(orc.kitti_project_sample_filter(ost, pc, P_PLUS_X, img, sem, None, H, W, KITTI_FILTERS))
+    st.append_kitti(frames, P_PLUS_X, H, W, KITTI_FILTERS)
+    st.check_status()
+    assert ost.n > 70 * 100
+    assert st.sizes().tolist() == sizes
+    assert np.array_equal(st.rows(), ost.rows())
+
+
+def test_k1_per_call_switches_change_no_bits(T, orc, monkeypatch):
+    """PCA_K1_QUEUES and PCA_K1_NO_INLINE are read on every call: a six-frame split batch (the K1 part of _ab_switches_child) under
+    the default, three queues, one queue and uploaded descriptors, switched inside this process -- the oracle's rows every time."""
+    monkeypatch.setenv('PCA_K1_MODE', 'split')
+    rng = np.random.default_rng(123)
+    H, W, n = 94, 352, 30000
+    P = np.array([[138., 0, 176, 0], [0, 138., 47, 0], [0, 0, 1, 0]]) @ np.linalg.inv(CAM_TO_VELO)
+    ost = orc.Store(6 * n)
+    frames, sizes = [], []
+    for _ in range(6):
+        pc = np.stack([rng.uniform(-40, 40, n), rng.uniform(-40, 40, n), rng.uniform(-2, 3, n), rng.uniform(0, 1, n)], 1).astype(np.float32)
+        img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        sem = rng.integers(0, 19, (H, W)).astype(np.uint8)
+        frames.append(dict(pts=cu(T, pc), rgb=cu(T, img), sem=cu(T, sem)))
+        sizes.append(orc.kitti_project_sample_filter(ost, pc, P, img, sem, None, H, W, KITTI_FILTERS))
+    assert ost.n > 20000
+    want = ost.rows()
+    for name, value in ((None, None), ('PCA_K1_QUEUES', '3'), ('PCA_K1_QUEUES', '1'), ('PCA_K1_NO_INLINE', '1')):
+        if name:
+            monkeypatch.setenv(name, value)
+        st = dev_store(capacity=6 * n, max_frames=8)
+        st.append_kitti(frames, P, H, W, KITTI_FILTERS)
+        st.check_status()
+        assert st.sizes().tolist() == sizes, (name, value)
+        assert np.array_equal(st.rows(), want), (name, value)
+        if name:
+            monkeypatch.delenv(name)
+
+
 def test_tile_kernel_start_offsets_change_nothing_in_a_subprocess():
     """PCA_BEV_STAGGER (read once per process; an experiment's knob, off by default): the workgroups of bev_tile_cells that share
     a CU start a few microseconds apart.  Timing only -- the golden BEV and the randomised configurations come out bit for bit."""
