@@ -82,7 +82,7 @@ struct pca_ctx {
     // mapped host memory the solve kernel stores into: the host polls it instead of copying and waiting
     uint32_t *icp_cnt = nullptr;      // dev [levels][cells]
     bool icp_cnt_dirty = true;        // not known to be all zero (first use, or a call that failed half way)
-    double *icp_host = nullptr;       // pinned + mapped [32]: T, fitness, rmse, iterations, flag; [31] = (call << 8 | pass) tag
+    double *icp_host = nullptr;       // pinned + mapped: the mirror of the ICP state block (pca_icp.hip, ICP_ST_* / ICP_HOST_*)
     double *icp_host_dev = nullptr;
     uint32_t icp_call = 0;
     // K1 deferred into the next raster (round 5): pca_kitti_integrate leaves the frame's K1 here when the mode is on; the next

@@ -14,17 +14,19 @@
 //                     grids; only the slabs (cells along z) the cloud occupies are scanned and searched
 //   icp_normals       per target point (8 lanes each): the K = 30 nearest neighbours (shell-by-shell grid search, exact
 //                     within the search cap), covariance, eigenvector of the smallest eigenvalue (cyclic Jacobi, f64)
-//   icp_match         per source point (8 lanes each): q = T p; from the third pass on, first the question whether the partner
-//                     of the last pass provably is still the unique nearest target (then no search); else the nearest target
+//   icp_match         per source point (16 lanes each in the first pass, 8 afterwards): q = T p; from the third pass on, first
+//                     the question whether the partner of the last pass provably is still the unique nearest target (then no
+//                     search); else the nearest target
 //                     (exact within the cap; the previous partner bounds the search from the start); the correspondence's
 //                     point-to-plane row r = (q - t).n, J = [q x n, n]; per workgroup one column of partial sums of J^T J,
 //                     J^T r, |q - t|^2, pair count (fixed order)
 //   icp_solve         30 workgroups, one per accumulator, add the columns up in a fixed order (deterministic); the last to
-//                     arrive takes the step: 6x6 Cholesky solve, T <- exp(x) T, fitness / rmse, convergence flag -- two
-//                     launches per iteration, and the host looks at the flag only every twelfth pass.
-// Measured on two 120 k-point sweeps: round 2 10.9 ms -> 2.8 ms per registration; round 4 2.71 -> 2.1 ms (grids 278 -> 131 us,
-// rows + solve 35 -> 9 us per pass, late passes 130 -> 80 us); what changed is in the comments of icp_cell_scan, icp_visit_shell,
-// icp_match and icp_solve_step, the measurements in profiles/r04_experiments/icp_second_session.txt.
+//                     arrive takes the step: 6x6 Cholesky solve, T <- exp(x) T, fitness / rmse, convergence flag, and
+//                     publishes the result and a news word in mapped host memory.
+// A pass is two launches (icp_match, icp_solve).  The host never copies or waits on the stream while a registration runs: it
+// polls the news word and stays ICP_AHEAD passes ahead of the device (icp_run_passes).  The state block the kernels and the
+// host share is mapped out once, at the ICP_ST_* constants; the workspace once, in icp_ws_layout.
+// Measurements behind the choices the comments name: profiles/r04_experiments/icp_second_session.txt, profiles/r05_experiments/icp_round5.txt.
 #include "pca_common.h"
 #include <cstring>
 #include <cstdio>
@@ -55,8 +57,48 @@ template <int LV> struct IcpLevel {
 #endif
 #define ICP_OCC __attribute__((amdgpu_waves_per_eu(ICP_WAVES_PER_EU)))
 #define ICP_NACC 30              // 21 (J^T J upper) + 6 (J^T r) + sum d^2 + inliers + sum r^2
-#define ICP_CHECK_EVERY 12        // the host looks at the convergence flag after every 12th pass (a look = a copy + a wait: 45 us of idle
-                                  // GPU; a pass after convergence = two early-exit launches: 9 us.  Registrations take 5-15 updates)
+
+// THE MAP of the state block (IcpArgs::state, doubles in device memory) and of its mirror (IcpArgs::host, mapped host
+// memory); every other comment points here.  icp_init writes [0, ICP_ST_CLEARED): [0, ICP_ST_INIT) from the host's IcpInit,
+// zero behind it.  icp_solve_step stores [0, ICP_ST_MIRRORED) into the state AND, slot for slot, into the mirror, then
+// releases the news word (icp_news_pack) behind those stores.
+enum : int {
+    ICP_ST_T = 0,                // [16] T, row-major (the last row is never written: it stays the init's)
+    ICP_ST_FITNESS = 16,         // of the latest evaluation
+    ICP_ST_RMSE = 17,
+    ICP_ST_PREV_FITNESS = 18,    // of the evaluation before: the convergence test compares the two
+    ICP_ST_PREV_RMSE = 19,
+    ICP_ST_ENDED = 20,           // != 0: converged, too few pairs or a singular system -- every later kernel leaves at once
+    ICP_ST_ITERS = 21,           // updates taken
+    ICP_ST_MIRRORED = 22,        // (end of the mirrored range)
+    ICP_ST_ZR = 24,              // IcpArgs::zr: four u32 in two doubles
+    ICP_ST_ARRIVED = 27,         // IcpArgs::arrived: one u32
+    ICP_ST_INIT = 32,            // (end of what IcpInit carries)
+    ICP_ST_T_PREV = 32,          // [12] T of the pass before (icp_match: how far has a point moved?)
+    ICP_ST_DBG = 48,             // [ICP_ST_DBG_N] PCA_ICP_DBG bit 0: searched queries per pass
+    ICP_ST_DBG_N = 16,
+    ICP_ST_CLEARED = 64,         // (end of what icp_init writes and of what the host copies back)
+    ICP_ST_SUMS = 64,            // [ICP_NACC] the accumulators of the running icp_solve (written before they are read)
+    ICP_ST_SIZE = 128,           // doubles the workspace holds for the block (icp_ws_layout)
+    ICP_HOST_NEWS = 31,          // mirror only: the news word, a uint64_t
+    ICP_HOST_SIZE = 32,          // doubles of the mirror
+};
+static_assert(ICP_ST_T + 16 <= ICP_ST_FITNESS && ICP_ST_ITERS < ICP_ST_MIRRORED && ICP_ST_MIRRORED <= ICP_ST_ZR, "T and the scalars");
+static_assert(ICP_ST_ZR + 2 <= ICP_ST_ARRIVED && ICP_ST_ARRIVED < ICP_ST_INIT, "zr and arrived start out with the init block");
+static_assert(ICP_ST_T_PREV >= ICP_ST_INIT && ICP_ST_T_PREV + 12 <= ICP_ST_DBG && ICP_ST_DBG + ICP_ST_DBG_N <= ICP_ST_CLEARED, "cleared part");
+static_assert(ICP_ST_SUMS >= ICP_ST_CLEARED && ICP_ST_SUMS + ICP_NACC <= ICP_ST_SIZE, "the sums end inside the block");
+static_assert(ICP_ST_MIRRORED <= ICP_HOST_NEWS && ICP_HOST_NEWS < ICP_HOST_SIZE, "the news word lies behind the mirrored range");
+
+// The news word: tag of the registration | ended << 8 | passes done.  icp_solve_step packs it, the host's poller
+// (IcpNews) unpacks it.  The passes have eight bits: pass + 1 must stay below 256, so with max_iter >= 255 the count runs
+// into the ended bit and reads as an end.  The call counter behind the tag wraps at 24 bits.
+struct IcpNewsWord { uint64_t tag; bool ended; int passes; };
+__host__ __device__ inline uint64_t icp_news_tag(uint32_t call) { return (uint64_t)call << 16; }
+__host__ __device__ inline uint64_t icp_news_pack(uint64_t tag, bool ended, int passes)
+{
+    return tag | (ended ? 0x100ull : 0ull) | (uint64_t)passes;
+}
+__host__ __device__ inline IcpNewsWord icp_news_unpack(uint64_t w) { return {w & ~0xffffull, (w & 0x100u) != 0, (int)(w & 0xffu)}; }
 
 struct IcpGrid {
     uint32_t *cnt;               // [cells] points per cell (counting pass), all zero again after the fill pass
@@ -74,13 +116,12 @@ struct IcpArgs {
     int32_t *nn_cell;            // [n_src] coarse cell the query lay in when it was searched last, -1 = outside the grid
     float *nn_slack;             // [n_src] how far the query may still move before its partner has to be searched again (icp_match)
     int no_skip;                 // PCA_ICP_NO_SKIP=1: every pass searches every query (A/B)
-    int dbg;                     // PCA_ICP_DBG bit 0: searched queries per pass counted in state[48 + pass] and printed by the host;
+    int dbg;                     // PCA_ICP_DBG bit 0: searched queries per pass counted at ICP_ST_DBG and printed by the host;
                                  // bits 1, 2: ablations of icp_normals (no eigen decomposition / no covariance pass), timing only
     uint64_t *lb_state;          // decoupled look-back of the cell scan
     uint32_t epoch;
     double *partial;             // [ICP_NACC][grid] partial sums, one column per workgroup of icp_match
-    double *state;               // [0..15] T (row-major), [16] fitness, [17] rmse, [18] prev fitness, [19] prev rmse,
-                                 // [20] converged flag, [21] iterations done, [24..25] zr, [32..43] T of the pass before
+    double *state;               // [ICP_ST_SIZE] the state block (ICP_ST_*)
     uint32_t *zr;                // [4] occupied slab range of the two grids: zmin, zmax of level 0, then of level 1 (cells along z;
                                  // zmin > zmax: no point inside).  Counting fills it; only these slabs are scanned and searched
     uint32_t *status;            // context status word
@@ -90,8 +131,8 @@ struct IcpArgs {
     double max_dist2;
     double rel_fitness, rel_rmse;
     int grid;
-    double *host;                // mapped host memory [32]: what icp_solve_step stores into state[0..21], and [31] = the tag
-    uint64_t tag;                // (call << 16) of this registration; icp_solve publishes tag | ended << 8 | passes done
+    double *host;                // [ICP_HOST_SIZE] the mirror in mapped host memory (ICP_ST_*, ICP_HOST_*)
+    uint64_t tag;                // icp_news_tag of this registration
     int pass;                    // number of this pass (0 = first)
 };
 
@@ -134,6 +175,23 @@ __device__ __forceinline__ IcpRun icp_run(int key)
 #define ICP_SCAN_PER 16                                    // cells per thread of the scan
 #define ICP_SCAN_TILE (ICP_SCAN_PER * ICP_SCAN_THREADS)
 
+// Four words -- min, max, min, max -- reduced over the NT threads of a workgroup (all must call it): thread i < 4 returns
+// word i, the others nothing of use
+template <int NT>
+__device__ __forceinline__ uint32_t icp_block_minmax4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3)
+{
+    __shared__ uint32_t s_w[NT / 64][4];
+    v0 = wave_reduce_min(v0); v1 = wave_reduce_max(v1); v2 = wave_reduce_min(v2); v3 = wave_reduce_max(v3);
+    if ((threadIdx.x & 63) == 0) { uint32_t *r = s_w[threadIdx.x >> 6]; r[0] = v0; r[1] = v1; r[2] = v2; r[3] = v3; }
+    __syncthreads();
+    uint32_t m = 0u;
+    if (threadIdx.x < 4) {
+        m = s_w[0][threadIdx.x];
+        for (int w = 1; w < NT / 64; ++w) m = (threadIdx.x & 1) ? (s_w[w][threadIdx.x] > m ? s_w[w][threadIdx.x] : m) : (s_w[w][threadIdx.x] < m ? s_w[w][threadIdx.x] : m);
+    }
+    return m;
+}
+
 // one thread per target point: its cell in both grids counted, and the slabs (cells along z) the cloud occupies -- the
 // grids are 64 slabs of 512 x 512 cells and a lidar sweep fills a quarter to a half of them: only those are scanned
 // (icp_cell_scan) and searched (icp_visit_shell treats every other slab as outside the grid; its start[] is never read)
@@ -155,35 +213,21 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_grid_count(const IcpArgs a)
     }
     // the workgroup's range into its row of zr_part: icp_cell_scan reduces the rows (no atomics: every wave of the launch runs at
     // once and sees the initial range, so even "only if it widens the range" meant 7500 atomics on four words -- 50-90 us)
-    __shared__ uint32_t s_z[ICP_THREADS / 64][4];
-    zlo0 = wave_reduce_min(zlo0); zhi0 = wave_reduce_max(zhi0); zlo1 = wave_reduce_min(zlo1); zhi1 = wave_reduce_max(zhi1);
-    if ((threadIdx.x & 63) == 0) { uint32_t *r = s_z[threadIdx.x >> 6]; r[0] = zlo0; r[1] = zhi0; r[2] = zlo1; r[3] = zhi1; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        uint32_t v = s_z[0][threadIdx.x];
-        for (int w = 1; w < ICP_THREADS / 64; ++w) v = (threadIdx.x & 1) ? (s_z[w][threadIdx.x] > v ? s_z[w][threadIdx.x] : v) : (s_z[w][threadIdx.x] < v ? s_z[w][threadIdx.x] : v);
-        a.zr_part[4 * blockIdx.x + threadIdx.x] = v;
-    }
+    const uint32_t m = icp_block_minmax4<ICP_THREADS>(zlo0, zhi0, zlo1, zhi1);
+    if (threadIdx.x < 4) a.zr_part[4 * blockIdx.x + threadIdx.x] = m;
 }
 
 // the range of occupied slabs from the rows icp_grid_count left (every workgroup of the scan for itself; 1024 threads)
 __device__ __forceinline__ void icp_reduce_range(const IcpArgs &a, uint32_t (&zr)[4])
 {
-    __shared__ uint32_t s_r[ICP_SCAN_THREADS / 64][4];
     __shared__ uint32_t s_zr[4];
     uint32_t v[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};
     for (int b = threadIdx.x; b < a.n_count_blocks; b += ICP_SCAN_THREADS) {
         const uint4 r = reinterpret_cast<const uint4 *>(a.zr_part)[b];
         v[0] = r.x < v[0] ? r.x : v[0]; v[1] = r.y > v[1] ? r.y : v[1]; v[2] = r.z < v[2] ? r.z : v[2]; v[3] = r.w > v[3] ? r.w : v[3];
     }
-    v[0] = wave_reduce_min(v[0]); v[1] = wave_reduce_max(v[1]); v[2] = wave_reduce_min(v[2]); v[3] = wave_reduce_max(v[3]);
-    if ((threadIdx.x & 63) == 0) { uint32_t *r = s_r[threadIdx.x >> 6]; r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3]; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        uint32_t m = s_r[0][threadIdx.x];
-        for (int w = 1; w < ICP_SCAN_THREADS / 64; ++w) m = (threadIdx.x & 1) ? (s_r[w][threadIdx.x] > m ? s_r[w][threadIdx.x] : m) : (s_r[w][threadIdx.x] < m ? s_r[w][threadIdx.x] : m);
-        s_zr[threadIdx.x] = m;
-    }
+    const uint32_t m = icp_block_minmax4<ICP_SCAN_THREADS>(v[0], v[1], v[2], v[3]);
+    if (threadIdx.x < 4) s_zr[threadIdx.x] = m;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) zr[i] = s_zr[i];
@@ -280,7 +324,7 @@ __device__ __forceinline__ IcpSlab icp_slab(const IcpArgs &a, int lv)
 
 // the records [s0, e) of a range of cells, four loads in flight (a one-record-per-trip loop is a chain of memory latencies:
 // measured 1 ms per 120 k queries, independent of how much the search is culled)
-// SGN > 1: SGN neighbouring lanes share one query; lane `sub` takes every SGN-th record, four loads in flight
+// SGN neighbouring lanes share one query; lane `sub` takes every SGN-th record
 template <int SGN, typename F>
 __device__ __forceinline__ void icp_scan_range_sg(const float4 *spts, uint32_t s0, uint32_t e, int sub, F &&f)
 {
@@ -294,32 +338,18 @@ __device__ __forceinline__ void icp_scan_range_sg(const float4 *spts, uint32_t s
     }
 }
 
-template <typename F>
-__device__ __forceinline__ void icp_scan_range(const float4 *spts, uint32_t s0, uint32_t e, F &&f)
-{
-    for (uint32_t q = s0; q < e; q += 4) {
-        const uint32_t last = e - 1;
-        const float4 w0 = spts[q], w1 = spts[q + 1 < e ? q + 1 : last], w2 = spts[q + 2 < e ? q + 2 : last],
-                     w3 = spts[q + 3 < e ? q + 3 : last];
-        f(w0);
-        if (q + 1 < e) f(w1);
-        if (q + 2 < e) f(w2);
-        if (q + 3 < e) f(w3);
-    }
-}
-
 // Visits every target point (its sorted record) of the shell of Chebyshev radius r around cell (cx,cy,cz) of grid LV,
 // skipping the cells whose box lies farther from the query (qx,qy,qz) than bound() -- the caller's current search radius
 // squared (after the own cell has produced a candidate a few centimetres away, almost every neighbour is culled).
 // A shell is walked as
 //   (1) its four faces made of whole rows of cells (|dz| = r, or |dy| = r): a row is ONE range of sorted points;
 //   (2) its two faces at |dx| = r: (2r-1)^2 single cells each, four lookups in flight.
-// SGN = 1: one lane does it all.  SGN = 8: eight neighbouring lanes share the query (sub = the lane's number in its
+// SGN (8 or 16) neighbouring lanes share the query (sub = the lane's number in its
 // group).  The LOOKUPS are dealt out piece by piece -- a far-field query that finds nothing walks ~2000 cells over its
-// shells -- and every range a lane finds non-empty is then SCANNED BY ALL EIGHT, record by record -- next to the sensor a
+// shells -- and every range a lane finds non-empty is then SCANNED BY THE WHOLE GROUP, record by record -- next to the sensor a
 // row of three cells holds hundreds of returns, and one lane scanning it alone was the slowest query of the launch
 // (measured per query with s_memrealtime: 0-5 m 36 us mean / 218 us max, beyond 20 m 13 us).  All loops have group-uniform
-// trip counts; the eight lanes must be converged at every call.
+// trip counts; the lanes of a group must be converged at every call.
 template <int LV, int SGN, typename B, typename F>
 __device__ __forceinline__ void icp_visit_shell(const IcpGrid &g, const IcpSlab sl, int cx, int cy, int cz, int r, double qx, double qy,
                                                 double qz, int sub, B &&bound, F &&f, const int rx = 0)
@@ -328,14 +358,11 @@ __device__ __forceinline__ void icp_visit_shell(const IcpGrid &g, const IcpSlab 
     // [cx - r, cx + r] and the two faces at |dx| = r are left out -- with rx >= r the cube of radius r is covered all the
     // same, by 8 r lookups instead of 8 r + 2 (2r - 1)^2.  For a query that has NO candidate yet nothing can be culled: over nine
     // coarse shells that is 289 lookups instead of 1650, and such queries (max-range returns, 245 us) are what a pass waits for.
+    static_assert(SGN == 8 || SGN == 16, "a group is 8 or 16 lanes");
     using G = IcpLevel<LV>;
     auto gap = [](double q, double lo) { return q < lo ? lo - q : (q > lo + G::cell ? q - (lo + G::cell) : 0.0); };
     // the ranges the lanes of the group hold in (s0, e0), each scanned by the whole group
     auto scan_found = [&](uint32_t s0, uint32_t e0) {
-        if (SGN == 1) {
-            if (e0 > s0) icp_scan_range(g.spts, s0, e0, f);
-            return;
-        }
         const int base = (int)(threadIdx.x & 63) & ~(SGN - 1);
         uint32_t bits = (uint32_t)(__ballot(e0 > s0) >> base) & ((1u << SGN) - 1u);
         while (bits) {
@@ -350,8 +377,7 @@ __device__ __forceinline__ void icp_visit_shell(const IcpGrid &g, const IcpSlab 
     if (r == 0) {
         if (cz < sl.lo || cz > sl.hi) return;               // (group-uniform) an empty slab: its start[] was never written
         const int c0 = icp_cell_index(x_lo, cy, cz);        // (the own cell, or the own row)
-        if (SGN == 1) icp_scan_range(g.spts, g.start[c0], g.start[c0 + (x_hi - x_lo) + 1], f);
-        else icp_scan_range_sg<SGN>(g.spts, g.start[c0], g.start[c0 + (x_hi - x_lo) + 1], sub, f);
+        icp_scan_range_sg<SGN>(g.spts, g.start[c0], g.start[c0 + (x_hi - x_lo) + 1], sub, f);
         return;
     }
     const int n = 2 * r + 1, m = 2 * r - 1;
@@ -473,13 +499,16 @@ __device__ __forceinline__ uint32_t icp_group_sum(uint32_t v)
     v += lane_xor_fetch<2>(v);
     return v + lane_xor_fetch<4>(v);
 }
+template <int S>
+__device__ __forceinline__ double icp_lane_xor_f64(double v)               // v of lane ^ S
+{
+    return __hiloint2double((int)lane_xor_fetch<S>((uint32_t)__double2hiint(v)), (int)lane_xor_fetch<S>((uint32_t)__double2loint(v)));
+}
 __device__ __forceinline__ double icp_group_sum(double v)
 {
-#define ICP_SUM_STAGE(S)                                                                                               \
-    v += __hiloint2double((int)lane_xor_fetch<S>((uint32_t)__double2hiint(v)), (int)lane_xor_fetch<S>((uint32_t)__double2loint(v)));
-    ICP_SUM_STAGE(1) ICP_SUM_STAGE(2) ICP_SUM_STAGE(4)
-#undef ICP_SUM_STAGE
-    return v;
+    v += icp_lane_xor_f64<1>(v);
+    v += icp_lane_xor_f64<2>(v);
+    return v + icp_lane_xor_f64<4>(v);
 }
 
 // icp_normals: per target point the K = 30 nearest neighbours, the covariance of everything within the K-th distance,
@@ -679,11 +708,11 @@ __device__ bool icp_solve_body(const IcpArgs &a, const double *sum, const IcpPre
     const double rmse = inl > 0 ? sqrt(sum[27] / inl) : 0.0;
     // Open3D evaluates fitness / rmse of the CURRENT transform, then updates; convergence compares successive evaluations
     const bool first = pv.iters == 0.0;
-    if (lane == 0) { S.put(16, fitness); S.put(17, rmse); }
+    if (lane == 0) { S.put(ICP_ST_FITNESS, fitness); S.put(ICP_ST_RMSE, rmse); }
     const bool conv = !first && fabs(pv.fit - fitness) < a.rel_fitness && fabs(pv.rmse - rmse) < a.rel_rmse;
-    if (icp_lane0(conv ? 1.0 : 0.0) != 0.0) { if (lane == 0) S.put(20, 1.0); return true; }
-    if (lane == 0) { S.put(18, fitness); S.put(19, rmse); }
-    if (inl < 6) { if (lane == 0) S.put(20, 1.0); return true; }    // (uniform: sum[] is shared)
+    if (icp_lane0(conv ? 1.0 : 0.0) != 0.0) { if (lane == 0) S.put(ICP_ST_ENDED, 1.0); return true; }
+    if (lane == 0) { S.put(ICP_ST_PREV_FITNESS, fitness); S.put(ICP_ST_PREV_RMSE, rmse); }
+    if (inl < 6) { if (lane == 0) S.put(ICP_ST_ENDED, 1.0); return true; }    // (uniform: sum[] is shared)
     // solve (J^T J) x = -J^T r  (Cholesky, upper triangle stored row-wise in sum[0..20]).  Every loop has a constant trip
     // count and no early exit, so the 6x6 system lives in registers (indexed dynamically it sat in scratch memory: ~100
     // dependent scratch round trips, most of the kernel's 55 us)
@@ -709,7 +738,7 @@ __device__ bool icp_solve_body(const IcpArgs &a, const double *sum, const IcpPre
             else A[i][j] = s * inv[j];
         }
     }
-    if (!ok) { if (lane == 0) S.put(20, 1.0); return true; }        // (uniform)
+    if (!ok) { if (lane == 0) S.put(ICP_ST_ENDED, 1.0); return true; }        // (uniform)
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         double s = b[i];
@@ -734,29 +763,27 @@ __device__ bool icp_solve_body(const IcpArgs &a, const double *sum, const IcpPre
                           -sb, cb * sa, cb * ca, x[5]};
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < 12; ++i) a.state[32 + i] = pv.T[i];   // (icp_match: how far has a point moved since the last pass?)
+        for (int i = 0; i < 12; ++i) a.state[ICP_ST_T_PREV + i] = pv.T[i];   // (icp_match: how far has a point moved since the last pass?)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                S.put(4 * i + j, U[4 * i] * pv.T[j] + U[4 * i + 1] * pv.T[4 + j] + U[4 * i + 2] * pv.T[8 + j] + (j == 3 ? U[4 * i + 3] : 0.0));
-        S.put(21, pv.iters + 1.0);
+                S.put(ICP_ST_T + 4 * i + j, U[4 * i] * pv.T[j] + U[4 * i + 1] * pv.T[4 + j] + U[4 * i + 2] * pv.T[8 + j] + (j == 3 ? U[4 * i + 3] : 0.0));
+        S.put(ICP_ST_ITERS, pv.iters + 1.0);
     }
     return false;
 }
-// the step, then the news for the host: tag | ended << 8 | passes done, released at system scope behind the stores above --
-// pca_icp_register polls that word in mapped memory instead of copying the state back and waiting for the stream
+// the step, then the news for the host (icp_news_pack), released at system scope behind the stores above -- the host polls
+// that word in mapped memory instead of copying the state back and waiting for the stream
 __device__ void icp_solve_step(const IcpArgs &a, const double *sum, const IcpPrev &pv)
 {
     const bool ended = icp_solve_body(a, sum, pv);
     if ((threadIdx.x & 63) == 0) {
         __threadfence_system();
-        __hip_atomic_store(reinterpret_cast<uint64_t *>(a.host + 31), a.tag | (ended ? 0x100ull : 0ull) | (uint64_t)(a.pass + 1),
+        __hip_atomic_store(reinterpret_cast<uint64_t *>(a.host + ICP_HOST_NEWS), icp_news_pack(a.tag, ended, a.pass + 1),
                            __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-
-
 
 // icp_match: ICP_SG neighbouring lanes share one source point.  The own cell's records and the rows of every further
 // shell are dealt out over the lanes, each lane keeps its own best partner, and at the end of every shell the lanes agree
@@ -769,6 +796,7 @@ struct IcpBest { double d2; int idx; float x, y, z; };
 template <int SG>
 __device__ __forceinline__ void icp_group_best(IcpBest &b)
 {
+    // (d2 not through icp_lane_xor_f64: fetching its halves in that order moves the compiled code)
 #define ICP_BEST_STAGE(S)                                                                                              \
     {                                                                                                                  \
         const uint32_t lo = lane_xor_fetch<S>((uint32_t)__double2loint(b.d2)), hi = lane_xor_fetch<S>((uint32_t)__double2hiint(b.d2)); \
@@ -793,14 +821,11 @@ __device__ __forceinline__ void icp_group_merge(IcpBest &b, double &other)
     // this lane's nearest that is not G: its best -- unless that IS G (it found G, or a second copy of it)
     double c = other;
     if (mine.idx >= 0 && mine.idx != b.idx && mine.d2 < c) c = mine.d2;
-#define ICP_MIN_STAGE(S)                                                                                               \
-    {                                                                                                                  \
-        const double od = __hiloint2double((int)lane_xor_fetch<S>((uint32_t)__double2hiint(c)), (int)lane_xor_fetch<S>((uint32_t)__double2loint(c))); \
-        c = od < c ? od : c;                                                                                           \
-    }
-    ICP_MIN_STAGE(1) ICP_MIN_STAGE(2) ICP_MIN_STAGE(4)
-    if (SG > 8) ICP_MIN_STAGE(8)
-#undef ICP_MIN_STAGE
+    auto least = [](double x, double y) { return x < y ? x : y; };
+    c = least(icp_lane_xor_f64<1>(c), c);
+    c = least(icp_lane_xor_f64<2>(c), c);
+    c = least(icp_lane_xor_f64<4>(c), c);
+    if (SG > 8) c = least(icp_lane_xor_f64<8>(c), c);
     other = c;
 }
 
@@ -828,7 +853,6 @@ __device__ __forceinline__ void icp_group_merge(IcpBest &b, double &other)
 // (PCA_ICP_NO_SKIP=1 switches it off: A/B).
 // SG lanes share a query: 8 from the second pass on; 16 in the FIRST pass, whose searches start from a partner decimetres off
 // and read several times the records (measured, 4 / 8 / 16 lanes: first pass 460 / 280 / 246 us, later full passes 178 / 112 / 125)
-#define ICP_QPW_MAX (ICP_THREADS / 8)     // queries per workgroup of icp_match, at most
 #define ICP_MARGIN 0.02                  // [m]
 template <int SG>
 __global__ __launch_bounds__(ICP_THREADS) ICP_OCC void icp_match(const IcpArgs a)
@@ -837,8 +861,8 @@ __global__ __launch_bounds__(ICP_THREADS) ICP_OCC void icp_match(const IcpArgs a
     __shared__ double s_row[ICP_QPW][8];                    // per query: J[0..5], r, |q - t|^2
     __shared__ uint32_t s_flag[ICP_QPW];                    // bit 0: has a partner, bit 1: the partner has a normal
     __shared__ double s_part[8][32];
-    if (a.state[20] != 0.0) return;                         // converged: the remaining passes are no-ops
-    const double *T = a.state;
+    if (a.state[ICP_ST_ENDED] != 0.0) return;               // ended: the remaining passes are no-ops
+    const double *T = a.state + ICP_ST_T;
     const int sub = threadIdx.x & (SG - 1);
     const int ql = threadIdx.x / SG;                    // query of the workgroup
     const int p = blockIdx.x * ICP_QPW + ql;
@@ -862,7 +886,7 @@ __global__ __launch_bounds__(ICP_THREADS) ICP_OCC void icp_match(const IcpArgs a
         const bool in_coarse = icp_cell_of<0>(qx, qy, qz, cx, cy, cz);
         need = true;
         if (!first && !a.no_skip && slack0 > 0.f) {
-            const double *O = a.state + 32;                 // T of the last pass
+            const double *O = a.state + ICP_ST_T_PREV;      // T of the last pass
             const double mx = qx - (O[0] * v.x + O[1] * v.y + O[2] * v.z + O[3]);
             const double my = qy - (O[4] * v.x + O[5] * v.y + O[6] * v.z + O[7]);
             const double mz = qz - (O[8] * v.x + O[9] * v.y + O[10] * v.z + O[11]);
@@ -886,7 +910,7 @@ __global__ __launch_bounds__(ICP_THREADS) ICP_OCC void icp_match(const IcpArgs a
             const double max_dist = sqrt(a.max_dist2);
             // (no slack is collected in the first two passes -- the updates that follow them move the points by decimetres, no
             // partner survives that -- so they cull against d1 itself, as a search without the shortcut would)
-            const double mg = a.state[21] >= 2.0 ? ICP_MARGIN : 0.0;
+            const double mg = a.state[ICP_ST_ITERS] >= 2.0 ? ICP_MARGIN : 0.0;
             double other = 1e300;                           // smallest squared distance of a seen target that is not the nearest
             double bnd = (max_dist + mg) * (max_dist + mg);     // cull bound: (d1 + margin)^2, d1 = the cap while there is no partner
             auto bound = [&]() { return bnd; };
@@ -976,7 +1000,7 @@ __global__ __launch_bounds__(ICP_THREADS) ICP_OCC void icp_match(const IcpArgs a
             }
         }
     }
-    if (a.dbg & 1) { const uint64_t m = __ballot(need && sub == 0); if ((threadIdx.x & 63) == 0 && m) { const int it = (int)a.state[21]; atomicAdd(&a.state[48 + (it < 15 ? it : 15)], (double)__popcll(m)); } }
+    if (a.dbg & 1) { const uint64_t m = __ballot(need && sub == 0); if ((threadIdx.x & 63) == 0 && m) { const int it = (int)a.state[ICP_ST_ITERS]; atomicAdd(&a.state[ICP_ST_DBG + (it < ICP_ST_DBG_N - 1 ? it : ICP_ST_DBG_N - 1)], (double)__popcll(m)); } }
     // the query's row (one lane of its group)
     if (sub == 0) {
         uint32_t flag = 0u;
@@ -1040,12 +1064,12 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve(const IcpArgs a)
     __shared__ double s_red[ICP_SOLVE_THREADS / 64];
     __shared__ double s_sum[32];
     __shared__ int s_last;
-    if (a.state[20] != 0.0) return;
+    if (a.state[ICP_ST_ENDED] != 0.0) return;
     IcpPrev pv;
     if (threadIdx.x < 64) {                                 // (every lane of wave 0 holds them: the values are uniform)
 #pragma unroll
-        for (int i = 0; i < 12; ++i) pv.T[i] = a.state[i];
-        pv.fit = a.state[18]; pv.rmse = a.state[19]; pv.iters = a.state[21];
+        for (int i = 0; i < 12; ++i) pv.T[i] = a.state[ICP_ST_T + i];
+        pv.fit = a.state[ICP_ST_PREV_FITNESS]; pv.rmse = a.state[ICP_ST_PREV_RMSE]; pv.iters = a.state[ICP_ST_ITERS];
     }
     const int k = blockIdx.x;
     const double *row = a.partial + (size_t)k * a.grid;
@@ -1064,7 +1088,7 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve(const IcpArgs a)
     if (threadIdx.x == 0) {
         double v = 0.0;
         for (int w = 0; w < ICP_SOLVE_THREADS / 64; ++w) v += s_red[w];
-        double *sums = a.state + 64;
+        double *sums = a.state + ICP_ST_SUMS;
         __hip_atomic_store(&sums[k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();                                    // release at agent scope: the sum, then the arrival
         const uint32_t t = atomicAdd(a.arrived, 1u);
@@ -1074,31 +1098,189 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve(const IcpArgs a)
     __syncthreads();
     if (!s_last) return;
     __threadfence();                                        // acquire: the sums the other XCDs released
-    if (threadIdx.x < 32) s_sum[threadIdx.x] = threadIdx.x < ICP_NACC ? __hip_atomic_load(a.state + 64 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    if (threadIdx.x < 32) s_sum[threadIdx.x] = threadIdx.x < ICP_NACC ? __hip_atomic_load(a.state + ICP_ST_SUMS + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     __syncthreads();
     if (threadIdx.x < 64) icp_solve_step(a, s_sum, pv);
 }
 
 // state block and "first pass" marks in one launch (a 512-byte copy from pageable memory and a memset before)
-struct IcpInit { double st[32]; };
+struct IcpInit { double st[ICP_ST_INIT]; };
 __global__ __launch_bounds__(ICP_THREADS) void icp_init(const IcpArgs a, const IcpInit in)
 {
     const int p = blockIdx.x * ICP_THREADS + threadIdx.x;
     if (p < a.n_src) a.nn_prev[p] = (int)0xfefefefe;        // "first pass" (see icp_match)
-    if (blockIdx.x == 0 && threadIdx.x < 64) a.state[threadIdx.x] = threadIdx.x < 32 ? in.st[threadIdx.x] : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x < ICP_ST_CLEARED) a.state[threadIdx.x] = threadIdx.x < ICP_ST_INIT ? in.st[threadIdx.x] : 0.0;
+}
+
+// ---- host side: pca_icp_register is argument checks and the steps below, in order ----
+static inline int icp_grid(int n, int sg) { const int qpw = ICP_THREADS / sg; return (n + qpw - 1) / qpw; }   // workgroups of icp_match<sg> = columns of partial sums
+static inline int icp_count_blocks(int n_tgt) { return (n_tgt + ICP_THREADS - 1) / ICP_THREADS; }              // workgroups of icp_grid_count / icp_grid_fill
+
+// The workspace: byte offsets of its regions from the 256-aligned base, and their sum; nothing else knows the regions.  (The
+// count tables are not among them: icp_ctx_prepare.)  Every region is constant or grows with n_src or n_tgt, so a workspace
+// that holds icp_ws_layout(m, m) holds icp_ws_layout(n_src, n_tgt) for all n_src, n_tgt <= m: pca_icp_register's size check.
+struct IcpWsLayout { int64_t start[2], spts[2], normal, nn_prev, nn_cell, nn_slack, partial, zr_part, state, total; };
+static IcpWsLayout icp_ws_layout(int64_t n_src, int64_t n_tgt)
+{
+    IcpWsLayout L;
+    L.total = 0;
+    auto take = [&L](int64_t bytes) { const int64_t at = L.total; L.total += pca_align256(bytes); return at; };
+    for (int lv = 0; lv < 2; ++lv) { L.start[lv] = take((ICP_CELLS + 1) * 4); L.spts[lv] = take(n_tgt * 16); }
+    L.normal = take(n_tgt * 16);
+    L.nn_prev = take(n_src * 4); L.nn_cell = take(n_src * 4); L.nn_slack = take(n_src * 4);
+    L.partial = take((int64_t)icp_grid((int)n_src, 16) * ICP_NACC * 8);    // (the first pass, 16 lanes per query, has the larger grid)
+    L.zr_part = take((int64_t)icp_count_blocks((int)n_tgt) * 16);
+    L.state = take(ICP_ST_SIZE * 8);
+    return L;
+}
+#define ICP_WS_BASE_SLACK 512    // room to align the caller's base pointer to 256
+
+// What the context owns.  The count tables: the fill pass leaves them all zero, so only a first use (or a call that failed
+// half way) clears them -- 2 x 67 MB of memset per registration otherwise.  The mapped mirror.  The scan's look-back tiles.
+static int icp_ctx_prepare(pca_ctx *ctx, hipStream_t s)
+{
+    const size_t cnt_bytes = (size_t)(2 * ICP_CELLS * 4);
+    if (!ctx->icp_cnt) { PCA_CHECK(ctx, hipMalloc(&ctx->icp_cnt, cnt_bytes)); ctx->icp_cnt_dirty = true; }
+    if (!ctx->icp_host) {
+        PCA_CHECK(ctx, hipHostMalloc(&ctx->icp_host, ICP_HOST_SIZE * sizeof(double), hipHostMallocMapped));
+        memset(ctx->icp_host, 0, ICP_HOST_SIZE * sizeof(double));
+        PCA_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->icp_host_dev), ctx->icp_host, 0));
+    }
+    if (ctx->icp_cnt_dirty) PCA_CHECK(ctx, hipMemsetAsync(ctx->icp_cnt, 0, cnt_bytes, s));
+    ctx->icp_cnt_dirty = true;                              // until this call has come through (icp_read_result)
+    return pca_ctx_reserve_tiles(ctx, 2 * (ICP_CELLS / ICP_SCAN_TILE), s);
+}
+
+// the rest of IcpArgs (the caller's part is filled in): the workspace's regions, the context's buffers, the switches, the tag
+static void icp_bind(pca_ctx *ctx, void *workspace, IcpArgs &a)
+{
+    char *const w = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
+    const IcpWsLayout L = icp_ws_layout(a.n_src, a.n_tgt);
+    for (int lv = 0; lv < 2; ++lv) {
+        a.g[lv].cnt = ctx->icp_cnt + (size_t)lv * ICP_CELLS;
+        a.g[lv].start = reinterpret_cast<uint32_t *>(w + L.start[lv]);
+        a.g[lv].spts = reinterpret_cast<float4 *>(w + L.spts[lv]);
+    }
+    a.normal = reinterpret_cast<float *>(w + L.normal);
+    a.nn_prev = reinterpret_cast<int32_t *>(w + L.nn_prev);
+    a.nn_cell = reinterpret_cast<int32_t *>(w + L.nn_cell);
+    a.nn_slack = reinterpret_cast<float *>(w + L.nn_slack);
+    a.partial = reinterpret_cast<double *>(w + L.partial);
+    a.zr_part = reinterpret_cast<uint32_t *>(w + L.zr_part);
+    a.state = reinterpret_cast<double *>(w + L.state);
+    a.zr = reinterpret_cast<uint32_t *>(a.state + ICP_ST_ZR);
+    a.arrived = reinterpret_cast<uint32_t *>(a.state + ICP_ST_ARRIVED);
+    a.n_count_blocks = icp_count_blocks(a.n_tgt);
+    a.grid = icp_grid(a.n_src, 16);
+    a.pass = 0;
+    a.no_skip = (int)PCA_ENV_ONCE("PCA_ICP_NO_SKIP", 0);
+    a.dbg = (int)PCA_ENV_ONCE("PCA_ICP_DBG", 0);
+    a.status = ctx->ticket + 1;
+    a.lb_state = ctx->tile_state;
+    a.host = ctx->icp_host_dev;
+    ctx->icp_call = (ctx->icp_call + 1) & 0xffffffu;
+    a.tag = icp_news_tag(ctx->icp_call);
+}
+
+// The host's end of the news word.  Opening it stores the tag of THIS call with nothing done yet.  (A kernel of an earlier
+// registration that could still store into the mirror does not exist: the passes behind the one that ended a registration
+// leave at their first line.)
+struct IcpNews {
+    uint64_t *word;
+    uint64_t tag;
+    bool ended = false, timed_out = false;
+    IcpNews(double *mirror, uint64_t t) : word(reinterpret_cast<uint64_t *>(mirror + ICP_HOST_NEWS)), tag(t) { __atomic_store_n(word, tag, __ATOMIC_RELEASE); }
+    IcpNewsWord poll() const                                // (a word with another tag says nothing)
+    {
+        const IcpNewsWord n = icp_news_unpack(__atomic_load_n(word, __ATOMIC_ACQUIRE));
+        return n.tag == tag ? n : IcpNewsWord{tag, false, 0};
+    }
+    void wait_for(int passes, double timeout_s)             // until that many passes have reported in, or `ended`, or `timed_out`
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t spins = 0;; ++spins) {
+            const IcpNewsWord n = poll();
+            if (n.ended) { ended = true; return; }
+            if (n.passes >= passes) return;
+#if defined(__x86_64__)
+            __builtin_ia32_pause();
+#endif
+            if ((spins & 1023u) == 1023u &&
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) { timed_out = true; return; }
+        }
+    }
+};
+
+// state block, mirror and "first pass" marks, then the target's grids and normals
+static void icp_build_target(pca_ctx *ctx, IcpArgs &a, const double *init, hipStream_t s)
+{
+    IcpInit in;
+    memset(&in, 0, sizeof in);
+    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    for (int i = 0; i < 16; ++i) in.st[ICP_ST_T + i] = init ? init[i] : eye[i];
+    const uint32_t zr0[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};           // zmin, zmax + 1 of both grids: nothing seen yet
+    memcpy(&in.st[ICP_ST_ZR], zr0, sizeof zr0);
+    for (int i = 0; i < ICP_ST_MIRRORED; ++i) ctx->icp_host[i] = in.st[i];   // (a registration that ends before any update returns init)
+    const dim3 per_point(icp_count_blocks(a.n_tgt)), threads(ICP_THREADS);
+    PCA_LAUNCH(ctx, PCA_K_ICP, icp_init, dim3((a.n_src + ICP_THREADS - 1) / ICP_THREADS), threads, s, a, in);
+    PCA_LAUNCH(ctx, PCA_K_ICP, icp_grid_count, per_point, threads, s, a);
+    a.epoch = pca_ctx_next_epoch(ctx, s);
+    PCA_LAUNCH(ctx, PCA_K_ICP, icp_cell_scan, dim3(2 * (ICP_CELLS / ICP_SCAN_TILE)), dim3(ICP_SCAN_THREADS), s, a);
+    PCA_LAUNCH(ctx, PCA_K_ICP, icp_grid_fill, per_point, threads, s, a);
+    PCA_LAUNCH(ctx, PCA_K_ICP, icp_normals, dim3(((int64_t)a.n_tgt * ICP_SG + ICP_THREADS - 1) / ICP_THREADS), threads, s, a);
+}
+
+// One more evaluation than updates: Open3D reports fitness / rmse of the final transform.  The host stays ICP_AHEAD passes
+// ahead of the device -- pass k is launched once pass k - ICP_AHEAD has reported in through the news word -- so the queue
+// never runs dry (a pass lasts 50-250 us, its two launches 10) and at most ICP_AHEAD no-op passes are in flight when the
+// registration ends.  Returns with news.ended or news.timed_out set.
+#define ICP_AHEAD 2
+#define ICP_POLL_TIMEOUT_S 2.0
+static void icp_run_passes(pca_ctx *ctx, IcpArgs &a, int max_iter, IcpNews &news, hipStream_t s)
+{
+    int launched = 0;
+    for (int it = 0; it <= max_iter; ++it) {
+        if (it >= ICP_AHEAD) news.wait_for(it - ICP_AHEAD + 1, ICP_POLL_TIMEOUT_S);
+        if (news.ended || news.timed_out) break;
+        if (it == max_iter) a.rel_fitness = a.rel_rmse = 1e300;              // last pass only evaluates
+        a.pass = it;
+        if (it == 0) { a.grid = icp_grid(a.n_src, 16); PCA_LAUNCH(ctx, PCA_K_ICP, icp_match<16>, dim3(a.grid), dim3(ICP_THREADS), s, a); }
+        else { a.grid = icp_grid(a.n_src, 8); PCA_LAUNCH(ctx, PCA_K_ICP, icp_match<8>, dim3(a.grid), dim3(ICP_THREADS), s, a); }
+        PCA_LAUNCH(ctx, PCA_K_ICP, icp_solve, dim3(ICP_NACC), dim3(ICP_SOLVE_THREADS), s, a);
+        ++launched;
+    }
+    while (!news.ended && !news.timed_out) news.wait_for(launched + 1, ICP_POLL_TIMEOUT_S);   // (the last pass launched ends the registration: it only evaluates)
+}
+
+struct IcpOut { double *T, *fitness, *rmse; int *iterations; };
+static int icp_read_result(pca_ctx *ctx, const IcpArgs &a, const IcpNews &news, const IcpOut &out, hipStream_t s)
+{
+    double st[ICP_ST_CLEARED] = {0};
+    if (news.timed_out || (a.dbg & 1)) {
+        // nothing heard for seconds (a launch that failed, a device in trouble), or the diagnostics' counters are wanted: the
+        // plain way -- copy the state back behind everything on the stream and wait
+        PCA_CHECK(ctx, hipMemcpyAsync(st, a.state, sizeof st, hipMemcpyDeviceToHost, s));
+        PCA_CHECK(ctx, hipStreamSynchronize(s));
+    } else {
+        for (int i = 0; i < ICP_ST_MIRRORED; ++i) st[i] = ctx->icp_host[i];  // (behind the acquire of the word that said "ended")
+    }
+    for (int i = 0; i < 12; ++i) out.T[i] = st[ICP_ST_T + i];
+    if (a.dbg & 1) { fprintf(stderr, "icp: searched queries per pass:"); for (int i = 0; i < ICP_ST_DBG_N; ++i) fprintf(stderr, " %.0f", st[ICP_ST_DBG + i]); fprintf(stderr, "\n"); }
+    out.T[12] = out.T[13] = out.T[14] = 0.0; out.T[15] = 1.0;
+    if (out.fitness) *out.fitness = st[ICP_ST_FITNESS];
+    if (out.rmse) *out.rmse = st[ICP_ST_RMSE];
+    if (out.iterations) *out.iterations = (int)st[ICP_ST_ITERS];
+    ctx->icp_cnt_dirty = news.timed_out;                    // the fill pass has run: every count is zero again
+    PCA_CHECK(ctx, hipGetLastError());
+    return 0;
 }
 
 extern "C" {
 
-static inline int icp_grid(int n, int sg = 16) { const int qpw = ICP_THREADS / sg; return (n + qpw - 1) / qpw; }   // workgroups of icp_match = columns of partial sums
-
 int64_t pca_icp_workspace_bytes(int32_t max_points)
 {
     if (max_points < 1) max_points = 1;
-    return 2 * (pca_align256(ICP_CELLS * 4) + pca_align256((ICP_CELLS + 1) * 4) + pca_align256((int64_t)max_points * 16)) +
-           pca_align256((int64_t)max_points * 16) + 3 * pca_align256((int64_t)max_points * 4) +
-           pca_align256((int64_t)icp_grid(max_points) * ICP_NACC * 8) + pca_align256((int64_t)((max_points + ICP_THREADS - 1) / ICP_THREADS) * 16) +
-           pca_align256(128 * 8) + 512;
+    return icp_ws_layout(max_points, max_points).total + ICP_WS_BASE_SLACK;
 }
 
 int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const float *tgt_pts, int32_t n_tgt,
@@ -1114,124 +1296,14 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     IcpArgs a;
     a.src = src_pts; a.tgt = tgt_pts; a.n_src = n_src; a.n_tgt = n_tgt;
-    char *w = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
-    const int64_t cells = (int64_t)ICP_NX * ICP_NY * ICP_NZ;
-    // the count tables belong to the context: the fill pass leaves them all zero, so only a first use (or a call that
-    // failed half way) clears them -- 2 x 67 MB of memset per registration otherwise
-    if (!ctx->icp_cnt) {
-        PCA_CHECK(ctx, hipMalloc(&ctx->icp_cnt, (size_t)(2 * cells * 4)));
-        ctx->icp_cnt_dirty = true;
-    }
-    if (!ctx->icp_host) {
-        PCA_CHECK(ctx, hipHostMalloc(&ctx->icp_host, 32 * sizeof(double), hipHostMallocMapped));
-        memset(ctx->icp_host, 0, 32 * sizeof(double));
-        PCA_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->icp_host_dev), ctx->icp_host, 0));
-    }
-    if (ctx->icp_cnt_dirty) PCA_CHECK(ctx, hipMemsetAsync(ctx->icp_cnt, 0, (size_t)(2 * cells * 4), s));
-    ctx->icp_cnt_dirty = true;                              // until this call has come through
-    for (int lv = 0; lv < 2; ++lv) {
-        a.g[lv].cnt = ctx->icp_cnt + (size_t)lv * cells; w += pca_align256(cells * 4);      // (the workspace's own slot stays unused)
-        a.g[lv].start = reinterpret_cast<uint32_t *>(w); w += pca_align256((cells + 1) * 4);
-        a.g[lv].spts = reinterpret_cast<float4 *>(w); w += pca_align256((int64_t)n_tgt * 16);
-    }
-    a.normal = reinterpret_cast<float *>(w); w += pca_align256((int64_t)n_tgt * 16);
-    a.nn_prev = reinterpret_cast<int32_t *>(w); w += pca_align256((int64_t)n_src * 4);
-    a.nn_cell = reinterpret_cast<int32_t *>(w); w += pca_align256((int64_t)n_src * 4);
-    a.nn_slack = reinterpret_cast<float *>(w); w += pca_align256((int64_t)n_src * 4);
-    a.no_skip = (int)PCA_ENV_ONCE("PCA_ICP_NO_SKIP", 0);
-    a.dbg = (int)PCA_ENV_ONCE("PCA_ICP_DBG", 0);
-    a.partial = reinterpret_cast<double *>(w); w += pca_align256((int64_t)icp_grid(n_src) * ICP_NACC * 8);
-    a.n_count_blocks = (n_tgt + ICP_THREADS - 1) / ICP_THREADS;
-    a.zr_part = reinterpret_cast<uint32_t *>(w); w += pca_align256((int64_t)a.n_count_blocks * 16);
-    a.state = reinterpret_cast<double *>(w);
-    a.zr = reinterpret_cast<uint32_t *>(a.state + 24);                 // initialised with the state block
-    a.status = ctx->ticket + 1;
-    a.arrived = reinterpret_cast<uint32_t *>(a.state + 27);            // zero with the state block
     a.max_dist2 = max_corr_dist * max_corr_dist;
     a.rel_fitness = rel_fitness; a.rel_rmse = rel_rmse;
-    a.grid = icp_grid(n_src);
-    a.host = ctx->icp_host_dev;
-    a.pass = 0;
-    // the word the host polls: tag of THIS call, nothing done yet.  (A kernel of an earlier registration that could still
-    // store into the mirror does not exist: the passes behind the one that ended a registration leave at their first line.)
-    ctx->icp_call = (ctx->icp_call + 1) & 0xffffffu;
-    a.tag = (uint64_t)ctx->icp_call << 16;
-    uint64_t *const tag_word = reinterpret_cast<uint64_t *>(ctx->icp_host + 31);
-    __atomic_store_n(tag_word, a.tag, __ATOMIC_RELEASE);
-    IcpInit in;
-    memset(&in, 0, sizeof in);
-    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    for (int i = 0; i < 16; ++i) in.st[i] = init ? init[i] : eye[i];
-    {
-        const uint32_t zr0[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};       // zmin, zmax + 1 of both grids: nothing seen yet
-        memcpy(&in.st[24], zr0, sizeof zr0);
-    }
-    for (int i = 0; i < 22; ++i) ctx->icp_host[i] = in.st[i];            // (a registration that ends before any update returns init)
-    const int scan_tiles = (int)(cells / ICP_SCAN_TILE);
-    if (pca_ctx_reserve_tiles(ctx, 2 * scan_tiles, s)) return -1;
-    a.lb_state = ctx->tile_state;
-    const dim3 per_point((n_tgt + ICP_THREADS - 1) / ICP_THREADS);
-    PCA_LAUNCH(ctx, PCA_K_ICP, icp_init, dim3((n_src + ICP_THREADS - 1) / ICP_THREADS), dim3(ICP_THREADS), s, a, in);
-    PCA_LAUNCH(ctx, PCA_K_ICP, icp_grid_count, per_point, dim3(ICP_THREADS), s, a);
-    a.epoch = pca_ctx_next_epoch(ctx, s);
-    PCA_LAUNCH(ctx, PCA_K_ICP, icp_cell_scan, dim3(2 * scan_tiles), dim3(ICP_SCAN_THREADS), s, a);
-    PCA_LAUNCH(ctx, PCA_K_ICP, icp_grid_fill, per_point, dim3(ICP_THREADS), s, a);
-    PCA_LAUNCH(ctx, PCA_K_ICP, icp_normals, dim3(((int64_t)n_tgt * ICP_SG + ICP_THREADS - 1) / ICP_THREADS), dim3(ICP_THREADS), s, a);
-    // One more evaluation than updates: Open3D reports fitness / rmse of the final transform.  The host stays ICP_AHEAD passes
-    // ahead of the device -- pass k is launched once pass k - ICP_AHEAD has reported in through the mapped word -- so the queue
-    // never runs dry (a pass lasts 50-250 us, its two launches 10) and at most ICP_AHEAD no-op passes are in flight when the
-    // flag comes up.  Round 4 copied the state back and waited every twelfth pass: three no-op passes per registration (30 us),
-    // 45 us of idle GPU per look, and a copy + wait at the end.
-    constexpr int ICP_AHEAD = 2;
-    constexpr double ICP_POLL_TIMEOUT_S = 2.0;
-    auto news = [&]() -> uint64_t {                         // low 16 bits of the word if it carries this call's tag, else 0
-        const uint64_t t = __atomic_load_n(tag_word, __ATOMIC_ACQUIRE);
-        return (t >> 16) == (a.tag >> 16) ? (t & 0xffffu) : 0u;
-    };
-    bool ended = false, timed_out = false;
-    auto wait_for = [&](int passes_done) {                  // until that many passes have reported in, or the registration has ended
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0;; ++spins) {
-            const uint64_t v = news();
-            if (v & 0x100u) { ended = true; return; }
-            if ((int)(v & 0xffu) >= passes_done) return;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-            if ((spins & 1023u) == 1023u &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > ICP_POLL_TIMEOUT_S) { timed_out = true; return; }
-        }
-    };
-    int launched = 0;
-    for (int it = 0; it <= max_iter && !ended && !timed_out; ++it) {
-        if (it >= ICP_AHEAD) wait_for(it - ICP_AHEAD + 1);
-        if (ended || timed_out) break;
-        if (it == max_iter) a.rel_fitness = a.rel_rmse = 1e300;              // last pass only evaluates
-        a.pass = it;
-        if (it == 0) { a.grid = icp_grid(n_src, 16); PCA_LAUNCH(ctx, PCA_K_ICP, icp_match<16>, dim3(a.grid), dim3(ICP_THREADS), s, a); }
-        else { a.grid = icp_grid(n_src, 8); PCA_LAUNCH(ctx, PCA_K_ICP, icp_match<8>, dim3(a.grid), dim3(ICP_THREADS), s, a); }
-        PCA_LAUNCH(ctx, PCA_K_ICP, icp_solve, dim3(ICP_NACC), dim3(ICP_SOLVE_THREADS), s, a);
-        ++launched;
-    }
-    while (!ended && !timed_out) wait_for(launched + 1);    // (the last pass launched ends the registration: it only evaluates)
-    double st[64] = {0};
-    if (timed_out || (a.dbg & 1)) {
-        // nothing heard for seconds (a launch that failed, a device in trouble), or the diagnostics' counters are wanted: the
-        // plain way -- copy the state back behind everything on the stream and wait
-        PCA_CHECK(ctx, hipMemcpyAsync(st, a.state, sizeof st, hipMemcpyDeviceToHost, s));
-        PCA_CHECK(ctx, hipStreamSynchronize(s));
-    } else {
-        for (int i = 0; i < 22; ++i) st[i] = ctx->icp_host[i];           // (behind the acquire of the word that said "ended")
-    }
-    for (int i = 0; i < 12; ++i) T_out[i] = st[i];
-    if (a.dbg & 1) { fprintf(stderr, "icp: searched queries per pass:"); for (int i = 0; i < 16; ++i) fprintf(stderr, " %.0f", st[48 + i]); fprintf(stderr, "\n"); }
-    T_out[12] = T_out[13] = T_out[14] = 0.0; T_out[15] = 1.0;
-    if (fitness) *fitness = st[16];
-    if (rmse) *rmse = st[17];
-    if (iterations) *iterations = (int)st[21];
-    ctx->icp_cnt_dirty = timed_out;                         // the fill pass has run: every count is zero again
-    PCA_CHECK(ctx, hipGetLastError());
-    return 0;
+    if (icp_ctx_prepare(ctx, s)) return -1;
+    icp_bind(ctx, workspace, a);
+    IcpNews news(ctx->icp_host, a.tag);
+    icp_build_target(ctx, a, init, s);
+    icp_run_passes(ctx, a, max_iter, news, s);
+    return icp_read_result(ctx, a, news, IcpOut{T_out, fitness, rmse, iterations}, s);
 }
 
 }  // extern "C"

@@ -73,7 +73,7 @@ class GpuIcp:
         lib = ctx.lib
         need = lib.pca_icp_workspace_bytes(int(max(source.shape[0], target.shape[0])))
         if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=target.device)
+            self._ws = torch.empty(int(need), dtype=torch.uint8, device=target.device)
         T = (C.c_double * 16)()
         fit, rmse, it = C.c_double(0), C.c_double(0), C.c_int(0)
         init_c = None if init is None else _lib.f64_array(np.asarray(init, dtype=np.float64), 16)

@@ -282,3 +282,85 @@ def test_icp_final_evaluation_equals_exact_nearest_neighbours(updates):
     assert 0 < (~inl).sum() < n_far                       # some far returns have no partner, most have one
     assert abs(r.fitness - inl.mean()) < 1e-12
     assert abs(r.inlier_rmse - np.sqrt((d[inl] ** 2).mean())) < 1e-9
+
+
+_SMALL = {}
+
+
+def small_pair():
+    """Two ~9 k-point sweeps 0.9 m apart, cast once and shared (read-only)."""
+    if not _SMALL:
+        for name, args in (('a', (0.0, 0.0, 0.0, 31)), ('b', (0.9, 0.03, 0.008, 32))):
+            pts = sweep(*args, n_beams=32, n_az=300)
+            pts.setflags(write=False)
+            _SMALL[name] = pts
+    return _SMALL['a'], _SMALL['b']
+
+
+def result_bytes(r):
+    """Pose, fitness, rmse and iteration count of an IcpResult as 19 doubles' bytes: equal bytes = bitwise equal."""
+    return np.concatenate([r.transformation.ravel(), [r.fitness, r.inlier_rmse, float(r.iterations)]]).astype(np.float64).tobytes()
+
+
+def register_c(src, tgt, ws_ptr, ws_bytes):
+    """pca_icp_register itself, with the defaults of GpuIcp; returns (rc, the 19 doubles' bytes)."""
+    import ctypes as C
+    from pca_amd import _lib
+    ctx = _lib.Context.get()
+    T = (C.c_double * 16)()
+    fit, rmse, it = C.c_double(0), C.c_double(0), C.c_int(0)
+    rc = ctx.lib.pca_icp_register(ctx.h, src.data_ptr(), int(src.shape[0]), tgt.data_ptr(), int(tgt.shape[0]), 1e3,
+                                  _lib.f64_array(np.eye(4), 16), 30, 1e-6, 1e-6, ws_ptr, ws_bytes, T, C.byref(fit),
+                                  C.byref(rmse), C.byref(it), ctx.stream())
+    return rc, np.array(list(T) + [fit.value, rmse.value, float(it.value)], dtype=np.float64).tobytes()
+
+
+def test_icp_ragged_sizes_through_an_exact_unaligned_workspace():
+    """n_src = 1 (mod 32), n_tgt = 1 (mod 256), n_src > n_tgt and, roles swapped, n_src < n_tgt: the C entry point with a
+    workspace of exactly pca_icp_workspace_bytes(max) bytes at a base that is not 256-aligned gives bitwise what
+    GpuIcp.register gives; one byte less is refused before anything is launched."""
+    import torch
+    from pca_amd import _lib
+    from pca_amd.icp import GpuIcp
+    a, b = small_pair()
+    n_long = (len(a) - 1) // 32 * 32 + 1
+    n_short = (min(len(b), n_long) - 2) // 256 * 256 + 1
+    assert n_long % 32 == 1 and n_short % 256 == 1 and 256 < n_short < n_long
+    long_, short = GpuIcp.to_device(a[:n_long]), GpuIcp.to_device(b[:n_short])
+    ctx = _lib.Context.get()
+    need = ctx.lib.pca_icp_workspace_bytes(n_long)
+    big = torch.empty(need + 512, dtype=torch.uint8, device=long_.device)
+    base = big.data_ptr() + 8
+    assert base % 256 == 8
+    for src, tgt in ((long_, short), (short, long_)):
+        ref = GpuIcp().register(src, tgt, 1e3, np.eye(4))
+        assert ref.iterations >= 3 and ref.fitness > 0.5               # a real registration
+        rc, got = register_c(src, tgt, base, need)
+        assert rc == 0, ctx.lib.pca_last_error(ctx.h)
+        assert got == result_bytes(ref)
+        assert ctx.status() == 0
+        rc, _ = register_c(src, tgt, base, need - 1)
+        assert rc == -1 and b'workspace too small' in ctx.lib.pca_last_error(ctx.h)
+        assert ctx.status() == 0
+
+
+def test_icp_one_context_changing_sizes():
+    """Large pair, a pair a third of its size, the large pair again on one GpuIcp: the third result is bitwise the first (the
+    count tables are zero again, the layout is worked out per call), the small one is what a fresh GpuIcp gives.  The
+    reported workspace size never shrinks with n and holds no slot for the count tables (they are the context's)."""
+    from pca_amd import _lib
+    from pca_amd.icp import GpuIcp
+    a, b = small_pair()
+    A = (GpuIcp.to_device(a), GpuIcp.to_device(b))
+    B = (GpuIcp.to_device(a[::3]), GpuIcp.to_device(b[::3]))
+    icp = GpuIcp()
+    first = icp.register(*A, 1e3, np.eye(4))
+    small = icp.register(*B, 1e3, np.eye(4))
+    third = icp.register(*A, 1e3, np.eye(4))
+    assert first.iterations >= 3 and first.fitness > 0.5 and small.iterations >= 3
+    assert result_bytes(third) == result_bytes(first)
+    assert result_bytes(small) == result_bytes(GpuIcp().register(*B, 1e3, np.eye(4)))
+    lib = _lib.Context.get().lib
+    sizes = [lib.pca_icp_workspace_bytes(n) for n in (1, 31, 32, 33, 255, 257, 4096, 9001, 120000, 1 << 20)]
+    assert all(lo <= hi for lo, hi in zip(sizes, sizes[1:]))
+    assert sizes[0] < 2 * 4 * 512 * 512 * 64 * 2
