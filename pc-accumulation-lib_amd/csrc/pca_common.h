@@ -174,6 +174,33 @@ struct Mat34 { double m[12]; };
 struct Mat44 { double m[16]; };
 struct ClassMask { uint64_t w[4]; };
 
+// loads through the global address space (pointers that arrive inside structs are generic to the compiler)
+template <typename T>
+__device__ __forceinline__ T pca_ldg(const T *p)
+{
+    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(reinterpret_cast<uintptr_t>(p));
+}
+// a value at a workgroup-uniform address in memory that nobody writes during the launch: one scalar load (s_load)
+template <typename T>
+__device__ __forceinline__ T pca_sload(const T *p)
+{
+    const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(((uintptr_t)hi << 32) | lo);
+}
+struct __attribute__((packed)) PcaU32u { uint32_t v; };
+__device__ __forceinline__ uint32_t pca_ldg_u32_unaligned(const uint8_t *p)     // one global_load_dword at any byte address
+{
+    return reinterpret_cast<const __attribute__((address_space(1))) PcaU32u *>(reinterpret_cast<uintptr_t>(p))->v;
+}
+typedef float pca_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 pca_ldg4(const float *p)      // one 16-byte global load
+{
+    const pca_f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) pca_f32x4 *>(reinterpret_cast<uintptr_t>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
 // (a select chain over the four words: `m.w[c >> 6]` with a per-lane class is a dynamically indexed read of the KERNEL
 // ARGUMENTS, which compiles to a vector load from the argument segment -- a memory round trip in the middle of the chain
 // class gather -> filter -> colour gather)

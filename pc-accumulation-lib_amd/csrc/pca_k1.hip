@@ -83,7 +83,7 @@ __device__ __forceinline__ void k1_append_body(const K1AppendArgs &a)
     __shared__ uint32_t s_w[BLK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t sum = 0;
-    for (int t = threadIdx.x; t < tile0; t += BLK) sum += k1_ldg(a.counts + t);
+    for (int t = threadIdx.x; t < tile0; t += BLK) sum += pca_ldg(a.counts + t);
     sum = wave_reduce_add(sum);
     if (lane == 0) s_w[wave] = sum;
     __syncthreads();
@@ -107,8 +107,8 @@ __device__ __forceinline__ void k1_append_body(const K1AppendArgs &a)
                 p = make_float4(v.x, v.y, v.z, v.w);
                 col = __builtin_nontemporal_load(rc + j);
             } else {
-                p = k1_ldg4(reinterpret_cast<const float *>(rp + j));
-                col = k1_ldg(rc + j);
+                p = pca_ldg4(reinterpret_cast<const float *>(rp + j));
+                col = pca_ldg(rc + j);
             }
             const int64_t o = base + j;
             if (o >= a.st.capacity) { overflow = true; continue; }

@@ -4,22 +4,6 @@
 #pragma once
 #include "pca_common.h"
 
-template <typename T>
-__device__ __forceinline__ T k1_ldg(const T *p)
-{
-    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(reinterpret_cast<uintptr_t>(p));
-}
-struct __attribute__((packed)) K1U32u { uint32_t v; };
-__device__ __forceinline__ uint32_t k1_ldg_u32_unaligned(const uint8_t *p)     // one global_load_dword at any byte address
-{
-    return reinterpret_cast<const __attribute__((address_space(1))) K1U32u *>(reinterpret_cast<uintptr_t>(p))->v;
-}
-typedef float k1_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 k1_ldg4(const float *p)      // one 16-byte global load
-{
-    const k1_f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) k1_f32x4 *>(reinterpret_cast<uintptr_t>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 __device__ __forceinline__ uint32_t k1_xcc_id() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u; }
 __device__ __forceinline__ int64_t k1_uniform_i64(int64_t v)
 {
@@ -62,7 +46,7 @@ __device__ __forceinline__ T k1_gather(const T *p)
 __device__ __forceinline__ uint32_t k1_gather_u32_unaligned(const uint8_t *p)
 {
 #if K1_GATHER_MODE == 0
-    return k1_ldg_u32_unaligned(p);
+    return pca_ldg_u32_unaligned(p);
 #else
     return k1_gather(reinterpret_cast<const uint32_t *>(p));      // (experiment builds only: the hardware takes the unaligned address)
 #endif
@@ -76,7 +60,7 @@ __device__ __forceinline__ float4 k1_load_point(const float *p, bool split)
         return make_float4(v.x, v.y, v.z, v.w);
     }
 #endif
-    return k1_ldg4(p);
+    return pca_ldg4(p);
 }
 
 #define K1_MAXQ 8
@@ -354,7 +338,7 @@ __device__ __forceinline__ void k1_body(const K1Args &a, const Tail &tail = Tail
             const uint32_t j = (uint32_t)(r * BLK) + threadIdx.x;
             unsigned c = 0;
             const bool act = j < ncand;
-            if (act) c = k1_ldg(fr.sem_gt + base_pt + s_cand[j]);
+            if (act) c = pca_ldg(fr.sem_gt + base_pt + s_cand[j]);
             packed[r] = c << 24;
             km[r] = __ballot(act && !((s_filt[c >> 5] >> (c & 31u)) & 1u));
         }
@@ -375,7 +359,7 @@ __device__ __forceinline__ void k1_body(const K1Args &a, const Tail &tail = Tail
         auto rgb_raw = [&](int pix, unsigned &sh) -> uint32_t {
             const int off = pix * 3;
             sh = off > last ? (unsigned)(off - last) * 8u : 0u;
-            return SPLIT ? k1_gather_u32_unaligned(fr.rgb + (off > last ? last : off)) : k1_ldg_u32_unaligned(fr.rgb + (off > last ? last : off));
+            return SPLIT ? k1_gather_u32_unaligned(fr.rgb + (off > last ? last : off)) : pca_ldg_u32_unaligned(fr.rgb + (off > last ? last : off));
         };
         auto rgb_at = [&](int pix) -> uint32_t { unsigned sh; const uint32_t w = rgb_raw(pix, sh); return (w >> sh) & 0xffffffu; };
 #pragma unroll
@@ -389,7 +373,7 @@ __device__ __forceinline__ void k1_body(const K1Args &a, const Tail &tail = Tail
                 ok[r] = j < ncand && px >= 0;
                 const int pix = ok[r] ? px : 0;                           // pixel 0 is always a valid address
                 // two gathers per point: the class byte and ONE unaligned dword holding r,g,b
-                cls[r] = SPLIT ? k1_gather(fr.sem + pix) : k1_ldg(fr.sem + pix);
+                cls[r] = SPLIT ? k1_gather(fr.sem + pix) : pca_ldg(fr.sem + pix);
                 pixr[r] = pix;
                 if (!BILIN) {
                     if (!dep) rgb[r] = rgb_raw(pix, rsh[r]);

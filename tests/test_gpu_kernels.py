@@ -194,6 +194,90 @@ def test_k1n_uv_outside_image_raises(T, golden):
         st.check_status()
 
 
+K1N_EDGE_FILTERS = [3, 70, 130, 199]                 # one class in each 64-bit word of the mask
+
+
+def k1n_edge_frames(T, sizes, seed=41):
+    """Small NuScenes-shaped frames around the 512-point tile of K1n: two cameras of 8 x 12 pixels, two image / class stacks
+    that alternate between frames, a different T per frame, camera indices -1..1 plus a few 7 (>= ncam: invalid, silently),
+    and in every non-empty frame one point whose nearest pixel is the LAST pixel of the last camera (a corner of its bilinear
+    footprint too): the 4-byte colour window is clamped at the end of the stack.  That pixel's class is 5 in both stacks, so
+    the planted point is kept.  Returns (host tuples, device frame dicts)."""
+    rng = np.random.default_rng(seed)
+    ncam, H, W = 2, 8, 12
+    stacks = []
+    for _ in range(2):
+        imgs = rng.integers(0, 256, (ncam, H, W, 3), dtype=np.uint8)
+        sems = rng.integers(0, 200, (ncam, H, W)).astype(np.uint8)
+        sems[ncam - 1, H - 1, W - 1] = 5
+        stacks.append((imgs, sems))
+    dev_stacks = [(cu(T, i), cu(T, s)) for i, s in stacks]
+    host, frames = [], []
+    for k, n in enumerate(sizes):
+        pc = np.stack([rng.uniform(-50, 50, n), rng.uniform(-50, 50, n), rng.uniform(-2, 4, n),
+                       rng.integers(0, 256, n).astype(float), rng.uniform(1.01, W - 1.01, n), rng.uniform(1.01, H - 1.01, n),
+                       rng.integers(-1, 5, n).astype(float)], 1).reshape(n, 7)
+        cam = rng.integers(-1, ncam, n)
+        if n > 8:
+            cam[[3, n // 3, n - 2]] = 7
+        if n:
+            cam[n // 2] = ncam - 1
+            pc[n // 2, 4:6] = [W - 1.4, H - 1.4]
+        a = 0.02 * (k + 1)
+        Tw = np.eye(4)
+        Tw[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        Tw[:3, 3] = [1.5 * k, -0.3 * k, 0.02 * k]
+        imgs, sems = stacks[k % 2]
+        host.append((pc, cam, imgs, sems, Tw))
+        frames.append(dict(pc=cu(T, pc), cam_idx=cu(T, cam), imgs=dev_stacks[k % 2][0], sems=dev_stacks[k % 2][1], T=Tw))
+    return host, frames
+
+
+@pytest.mark.parametrize('sample_mode', ['nearest', 'bilinear'])
+def test_k1n_batch_and_single_forms_agree_at_tile_edges(T, orc, sample_mode):
+    """The batch form (append_nusc_many, two calls: the second starts at a non-zero first_slot and reuses the staging) and the
+    single-frame form (append_nusc) store the same rows and offsets, and every frame's rows are the oracle's, bit for bit:
+    an empty frame, one point, one short of / exactly / one past the 512-point tile, three tiles with a one-point last tile,
+    a trailing empty frame."""
+    sizes = [0, 1, 511, 512, 513, 1025, 0]
+    host, frames = k1n_edge_frames(T, sizes)
+    many = dev_store(capacity=sum(sizes) + 16, max_frames=16, intensity_div255=True)
+    many.append_nusc_many(frames[:3], K1N_EDGE_FILTERS, sample_mode=sample_mode)
+    many.append_nusc_many(frames[3:], K1N_EDGE_FILTERS, sample_mode=sample_mode)
+    one = dev_store(capacity=sum(sizes) + 16, max_frames=16, intensity_div255=True)
+    for f in frames:
+        one.append_nusc(f['pc'], f['cam_idx'], f['imgs'], f['sems'], f['T'], K1N_EDGE_FILTERS, sample_mode=sample_mode)
+    many.check_status()
+    one.check_status()
+    assert np.array_equal(many.offsets(), one.offsets())
+    assert np.array_equal(many.rows(), one.rows())
+    got = many.frame_rows()
+    assert len(got) == len(sizes)
+    kept = 0
+    orc.set_sample_mode(1 if sample_mode == 'bilinear' else 0)
+    try:
+        for (pc, cam, imgs, sems, Tw), rows in zip(host, got):
+            ost = orc.Store(max(pc.shape[0], 1), intensity_div255=True)
+            orc.nusc_sample_filter_transform(ost, pc, cam, imgs, sems, Tw, K1N_EDGE_FILTERS)
+            assert np.array_equal(rows, ost.rows())
+            kept += ost.n
+    finally:
+        orc.set_sample_mode(0)
+    assert 0 < kept < sum(sizes)
+
+
+def test_k1n_batch_uv_outside_image_raises(T):
+    host, frames = k1n_edge_frames(T, [513, 600])
+    pc, cam = host[1][0].copy(), host[1][1].copy()
+    pc[5, 4] = 0.5                                   # u <= 1 for a point assigned to a camera
+    cam[5] = 1
+    frames[1] = dict(frames[1], pc=cu(T, pc), cam_idx=cu(T, cam))
+    st = dev_store(capacity=2048, max_frames=4, intensity_div255=True)
+    st.append_nusc_many(frames, K1N_EDGE_FILTERS)
+    with pytest.raises(AssertionError):
+        st.check_status()
+
+
 def test_k0n_project_cams_golden(T, orc, golden):
     from datasets.nuscenes_utils import project_to_cameras
     g = golden('utils')
