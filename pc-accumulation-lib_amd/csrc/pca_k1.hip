@@ -37,6 +37,8 @@
 // Host side: one K1Call (what a call's plans share) and one K1Plan per launch -- FUSED one; SPLIT (512 x 4 tiles) one per sub-batch
 // (k1_cut_batches), all over ONE workspace (k1_ws_layout).  Kernels by table; every PCA_K1_* switch is read in k1_tuning.
 #include "pca_common.h"
+#include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -212,7 +214,7 @@ static void k1_fill_camera(pca_ctx *ctx, const K1Call &c, int first_slot, K1Args
     a.H = c.H; a.W = c.W; a.sample_mode = c.sample_mode;
     // f32 rows and the error bound of the conservative test: 2^-19 relative is 6x the worst case of three
     // rounded coefficients and four fma roundings per form (< 2^-21.6), so a point is only ever culled when its
-    // exact f64 projection is outside the frustum by a wide margin
+    // exact f64 projection is outside the frustum by a wide margin -- as long as no form overflows (cull[16] below)
     const double g = 1.0 / 524288.0;
     const double wh = (double)(c.W > c.H ? c.W : c.H) + 1.0;
     double sx = 0, sy = 0, sd = 0;
@@ -222,6 +224,15 @@ static void k1_fill_camera(pca_ctx *ctx, const K1Call &c, int first_slot, K1Args
     a.cull[13] = (float)(g * (fabs(P[3]) + fabs(P[7]) + wh * fabs(P[11])) * 1.0000002 + 1e-30);
     a.cull[14] = (float)((double)c.W - 0.5);
     a.cull[15] = (float)((double)c.H - 0.5);
+    // The bound above is one of rounding errors: it says nothing once a form or a partial sum of its chain overflows.  Each is at
+    // most A max|xyz| + B in magnitude; while that stays below FLT_MAX / 4 nothing overflows (f32 roundings included).  Beyond the
+    // max|xyz| of cull[16] the kernel culls nothing.
+    const double A = sx + sy + wh * sd;
+    const double B = fabs(P[3]) + fabs(P[7]) + wh * fabs(P[11]);
+    const double lim = ((double)FLT_MAX / 4 - B) / A;              // (A = 0: +inf)
+    if (!(lim > 0)) a.cull[16] = -1.0f;                            // a huge or NaN P: every max|xyz| is beyond it
+    else if (lim >= (double)FLT_MAX) a.cull[16] = FLT_MAX;         // only inf is beyond it
+    else a.cull[16] = nextafterf((float)lim, 0.0f);                // (rounded towards the safe side)
     for (int i = 0; i < 4; ++i) a.filt.w[i] = c.filter_mask ? c.filter_mask[i] : 0;
     a.st = *c.store; a.frame_off = c.frame_off; a.first_slot = first_slot;
     a.status = ctx->ticket + 1;

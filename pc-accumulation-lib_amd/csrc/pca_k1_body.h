@@ -77,7 +77,8 @@ struct K1Args {
     int qtiles[K1_MAXQ];                // SPLIT: tiles in queue q
     Mat34 P;
     int H, W;
-    float cull[16];                     // f32 rows x[4] y[4] d[4] of P, then s, c (error bound = s*max|xyz| + c), W-.5, H-.5
+    float cull[17];                     // f32 rows x[4] y[4] d[4] of P, then s, c (error bound = s*max|xyz| + c), W-.5, H-.5,
+                                        // and the max|xyz| beyond which a form may leave the f32 range: no cull there
     ClassMask filt;
     pca_store st;                       // FUSED
     int64_t *frame_off;
@@ -258,7 +259,10 @@ __device__ __forceinline__ void k1_body(const K1Args &a, const Tail &tail = Tail
     // ---------------- phase 1: conservative frustum test of every point ----------------
     // f32 estimates of the three projection rows, two points per packed instruction; a point is dropped only if one of
     //   depth, u + 0.5 depth, (W - 0.5) depth - u, v + 0.5 depth, (H - 0.5) depth - v
-    // is below minus the error bound (NaN / inf never drop a point: every compare is false)
+    // is below minus the error bound.  The bound holds while every form and every partial sum stays finite in f32: beyond
+    // max|xyz| = cull[16] (host: k1_fill_camera) a form can overflow to -inf next to a finite bound, so there the bound is
+    // +inf and nothing is dropped.  NaN never drops a point (every compare is false; fmaxf skips it, and it is in every form),
+    // +-inf never does either (max|xyz| = inf is beyond the limit).
     typedef float f2 __attribute__((ext_vector_type(2)));
     uint64_t cm[PPT];
     float4 v[PPT];
@@ -283,7 +287,9 @@ __device__ __forceinline__ void k1_body(const K1Args &a, const Tail &tail = Tail
                 x.x = v[k].x; x.y = v[k + 1].x; y.x = v[k].y; y.y = v[k + 1].y; z.x = v[k].z; z.y = v[k + 1].z;
                 m.x = fmaxf(fmaxf(fabsf(x.x), fabsf(y.x)), fabsf(z.x));
                 m.y = fmaxf(fmaxf(fabsf(x.y), fabsf(y.y)), fabsf(z.y));
-                const f2 M = __builtin_elementwise_fma(sp(cu[12]), m, sp(cu[13]));       // error bound of every form
+                f2 M = __builtin_elementwise_fma(sp(cu[12]), m, sp(cu[13]));             // error bound of every form
+                M.x = m.x > cu[16] ? __builtin_huge_valf() : M.x;                        // (a compare and a select, no branch)
+                M.y = m.y > cu[16] ? __builtin_huge_valf() : M.y;
                 const f2 fx = __builtin_elementwise_fma(sp(cu[2]), z, __builtin_elementwise_fma(sp(cu[1]), y, __builtin_elementwise_fma(sp(cu[0]), x, sp(cu[3]))));
                 const f2 fy = __builtin_elementwise_fma(sp(cu[6]), z, __builtin_elementwise_fma(sp(cu[5]), y, __builtin_elementwise_fma(sp(cu[4]), x, sp(cu[7]))));
                 const f2 d = __builtin_elementwise_fma(sp(cu[10]), z, __builtin_elementwise_fma(sp(cu[9]), y, __builtin_elementwise_fma(sp(cu[8]), x, sp(cu[11]))));

@@ -1050,6 +1050,41 @@ def case_sweeps(ref, out_dir):
     print('nusc_sweeps written:', out['points'].shape, len(res['instances_token']), 'labelled boxes')
 
 
+def case_k1_edges(ref, out_dir):
+    """The reference's velo2img / gen_semantic_pc / filter_semseg_pc on the frames of tests/k1_edges_common.py (points at the
+    frustum's planes and their f32 neighbours, a ladder of magnitudes up to FLT_MAX, special values): one file per camera with
+    the points, the per-point mask, u / v of the masked points and the indices kept after the class filter.  The image and
+    the class map are drawn from the case's seed and not stored.  The intensity column carries the point's index through the
+    reference (it copies the column; the stored points hold the case's own intensities)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import k1_edges_common as kc
+    for name in kc.CASES:
+        fr = kc.frame(name)
+        pts, P, H, W, filters, seed = fr.case()
+        img, sem = kc.image_of(seed, H, W)
+        acc = ref.kitti.Kitti360SemanticPointCloudAccumulator(
+            8., {'h_velo_cam': np.eye(4), 'p_cam_frame': P, 'p_velo_frame': P}, 1e3, None, filters, SEM_IDXS, True, BEV_PARAMS_KITTI)
+        n = pts.shape[0]
+        tagged = pts.astype(np.float64)
+        tagged[:, 3] = np.arange(n)
+        with np.errstate(all='ignore'):
+            vi = acc.velo2img(tagged.copy(), P, H, W)
+            rgb = acc.gen_semantic_pc(tagged.copy(), img, P)
+            cls = acc.gen_semantic_pc(tagged.copy(), sem.astype(np.int64)[..., None], P)
+            kept = acc.filter_semseg_pc(np.concatenate((rgb, cls[:, -1:]), axis=1))
+        idx = vi[:, 3].astype(np.int64)
+        assert np.array_equal(tagged[idx, :3], vi[:, :3]) and np.array_equal(rgb[:, 3], vi[:, 3]) and np.array_equal(cls[:, 3], vi[:, 3])
+        mask = np.zeros(n, bool)
+        mask[idx] = True
+        assert np.array_equal(np.flatnonzero(mask), idx)                 # the reference keeps the order
+        u, v = vi[:, 4].astype(np.int64), vi[:, 5].astype(np.int64)
+        assert np.array_equal(rgb[:, 4:7], img[v, u]) and np.array_equal(cls[:, 4], sem[v, u])
+        out = dict(pts=pts, mask=mask, u=u.astype(np.int16), v=v.astype(np.int16), kept=kept[:, 3].astype(np.int32))
+        path = os.path.join(out_dir, f'k1_edges_{name}.npz')
+        np.savez_compressed(path, **out)
+        print(f'k1_edges_{name}: {n} points, {int(mask.sum())} in the image, {len(kept)} kept, {os.path.getsize(path)} bytes')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(
@@ -1061,8 +1096,8 @@ def main():
     np.random.seed(0)
     ref = import_reference()
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
-                 bev_edges=case_bev_edges, nusc=case_nusc, utils=case_utils,
-                 sweeps=case_sweeps)
+                 bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
+                 utils=case_utils, sweeps=case_sweeps)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
