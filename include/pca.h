@@ -304,6 +304,40 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
                           void *workspace /*dev*/, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * BEV planes of ANY semantic class group, all groups counted in one pass over the window.  Replaces
+ *       bev_generator/bev_generator.py:373-394 (gen_sem_probmap: partition by a list of classes, two count maps,
+ *       dirichlet expectation), :417-436 (partition_semantic_pc), :438-455 (gen_gridmap_count_map), :457-480
+ *       (dirichlet_dist_expectation) for the static partition of the window (sem_bev.py:57-69), and the geometry of
+ *       bev_generator/bev_generator.py:127-160, :207-255, :737-747 exactly as the rasteriser above evaluates it
+ *       (owed re-transforms oldest first, origin, R, dx / dy, strict crop, z < height_filter, dyn != 1, floor to the grid,
+ *       clamp, image rows; a point whose z is not finite is dropped).
+ *     groups[g]: the 256-bit class set of group g, laid out like pca_bev_params.dynobj_mask; groups may overlap.
+ *     Per (cell, set) with n static points, n_g of them in group g:  prob = (n_g + 1) / ((n_g + 1) + ((n - n_g) + 1)).
+ *     Output (dev, any of them may be NULL, not all): prob f64 / prob_f16 [3 sets][n_groups][px][px], counts u32
+ *       [3 sets][n_groups + 1][px][px] (slot n_groups = all static points); set order {present, future, full}.
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
+ *     Grid: 1 <= px <= 1024 (else "bev class planes: px must be in 1..1024": no banding); 1 <= n_groups <= 16.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to what is read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a bin range
+ *     armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared (the whole window is read).  A window above
+ *     max_points is cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives prob 0.5 and counts 0.
+ *     Every argument is checked before anything is launched; -1 with pca_last_error set.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_BEV_MAX_CLASS_GROUPS 16
+typedef struct { uint64_t mask[4]; } pca_class_group;      /* 256-bit class set, laid out like dynobj_mask */
+int64_t pca_bev_class_workspace_bytes(int64_t max_points, int px);
+int pca_bev_class_planes(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                         int slot_begin, int slot_split, int slot_end, int64_t max_points,
+                         const pca_bev_params *prm,
+                         const pca_class_group *groups, int n_groups,
+                         const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                         void *workspace /*dev*/, int64_t workspace_bytes,
+                         double *prob      /*dev [3][n_groups][px][px]   or NULL*/,
+                         uint16_t *prob_f16/*dev, same shape             or NULL*/,
+                         uint32_t *counts  /*dev [3][n_groups+1][px][px] or NULL; slot n_groups = all static points*/,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -496,7 +530,8 @@ int64_t pca_host_track_trigger(pca_host_track *t, double bev_horizon, int64_t pr
  * ------------------------------------------------------------------------------------------------ */
 enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
-    PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP, PCA_K_COUNT
+    PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
+    PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

@@ -126,6 +126,9 @@ class SemBEVGenerator(BEVGenerator):
         self.dyn_idx = 9             # column of the dynamic flag
         self.rgb_fill = rgb_fill
         self._frame = None
+        # extension (off while empty): extra class planes in every sample, plane name -> list of sem_idxs names or integer
+        # classes, e.g. {'sidewalk': [1], 'vehicle': ['car', 'truck', 'bus', 'motorcycle']} -> keys '<name>_<set>'
+        self.sem_planes = {}
 
     # ------------------------------------------------------------------------------------------
     def generate_bev_device(self, pc_present, pc_future, pc_full, want_f64=False, out16=None):
@@ -146,10 +149,17 @@ class SemBEVGenerator(BEVGenerator):
             pc_present, pc_future, pc_full = (self._grid_rows_to_metres(p) for p in (pc_present, pc_future, pc_full))
         device_only, self._device_only = self._device_only, False
         out16, self._out16 = self._out16, None
+        names, groups = self._sem_plane_groups()
+        frame = self._frame if self._frame is not None else (np.eye(3), 0., 0., float(self.view_size))
         p16, _ = self.generate_bev_device(pc_present, pc_future, pc_full, out16=None if self.do_warp else out16)
         self._frame = None
+        # the class planes come after the 21 planes, in the same frame
+        c16 = self.class_planes_device(pc_present, pc_future, pc_full, groups, *frame)[0] if names else None
         if getattr(pc_present, 'window', None) is not None and pc_present.window.future_is_present:
             p16[7:14] = p16[0:7]             # generate_bev(present_idx=None, gen_future=True): every set is the window
+            if c16 is not None:
+                c16[1] = c16[0]
+                c16[2] = c16[0]
         if self.do_warp:
             # polynomial warp augmentation: planes on the device (pca_bev_warp), trajectory vertices on the host
             px = self.pixel_size
@@ -158,6 +168,8 @@ class SemBEVGenerator(BEVGenerator):
             a_1, a_2 = self.cal_warp_params(i_warp, i_mid, px - 1)
             b_1, b_2 = self.cal_warp_params(j_warp, j_mid, px - 1)
             p16 = self.warp_planes_device(p16, a_1, a_2, b_1, b_2, out16)
+            if c16 is not None:
+                c16 = self.warp_planes_device(c16.view(-1, px, px), a_1, a_2, b_1, b_2).view(3, len(names), px, px)
             args = (a_1, a_2, b_1, b_2, i_mid, j_mid, i_warp, j_warp)
             trajs_present = self.warp_trajs(trajs_present, *args)
             trajs_future = self.warp_trajs(trajs_future, *args)
@@ -169,8 +181,90 @@ class SemBEVGenerator(BEVGenerator):
                    'trajs_full': trajs_full}
             if gt_lane_trajs is not None:
                 out['gt_lanes'] = gt_lane_trajs
+            if c16 is not None:
+                out['sem_planes_f16'], out['sem_plane_names'] = c16, names
             return out
-        return self.pack_bev(p16.cpu().numpy(), trajs_present, trajs_future, trajs_full, gt_lane_trajs)
+        bev = self.pack_bev(p16.cpu().numpy(), trajs_present, trajs_future, trajs_full, gt_lane_trajs)
+        if c16 is not None:
+            c = c16.cpu().numpy()
+            for s, set_name in enumerate(SETS):
+                for k, name in enumerate(names):
+                    bev[f'{name}_{set_name}'] = c[s, k]
+        return bev
+
+    # ---- class planes (extension: pca_bev_class_planes) --------------------------------------------
+    RESERVED_PLANE_NAMES = ('road', 'intensity', 'rgb', 'dynamic', 'elevation', 'trajs')
+
+    def _classes_of(self, sem_clss):
+        """sem_idxs names (an unknown one raises KeyError, as the reference's lookup does) or integer classes -> integers."""
+        return [self.sem_idxs[c] if isinstance(c, str) else int(c) for c in sem_clss]
+
+    def _sem_plane_groups(self):
+        """(plane names, class-index lists) of `sem_planes`."""
+        planes = getattr(self, 'sem_planes', None) or {}
+        for name in planes:
+            if name in self.RESERVED_PLANE_NAMES:
+                raise ValueError(f"sem_planes: '{name}' is the name of one of the sample's own planes")
+        return list(planes), [self._classes_of(v) for v in planes.values()]
+
+    def class_planes_device(self, pc_present, pc_future, pc_full, groups, rot_mat, dx, dy, aug_view_size, want_counts=False):
+        """(prob_f16, prob_f64, counts | None), cuda [3, len(groups) (+ 1), px, px]: the planes of the class groups over the
+        static points of the three sets, in the frame the 21 planes are rasterised in (DeviceStore.bev_class_planes)."""
+        if isinstance(pc_present, WindowPart):
+            w = pc_present.window
+            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
+            return w.store.bev_class_planes(w.split, prm, groups, first_frame=w.first, last_frame=w.last,
+                                            want_counts=want_counts)
+        # host arrays go through the temporary stores, as in rasterise: 'full' is an input of its own
+        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
+        st = self._tmp_store('pf')
+        st.load_rows([pc_present, pc_future])
+        a = st.bev_class_planes(1, prm, groups, want_counts=want_counts)
+        st2 = self._tmp_store('full')
+        st2.load_rows([pc_full])
+        b = st2.bev_class_planes(1, prm, groups, want_counts=want_counts)
+        for x, y in zip(a, b):
+            if x is not None:
+                x[2] = y[0]
+        return a
+
+    def _class_counts_from_grid_rows(self, pc, groups):
+        """Pre-gridded rows (columns 0, 1 = cell indices) -> (prob f64 [len(groups), px, px], counts [len(groups) + 1, px,
+        px]) of ALL the rows: no static partition, no height filter -- these helpers reduce whatever rows they are given."""
+        rows = np.array(pc, dtype=np.float64)
+        px = self.pixel_size
+        rows[:, 0:2] = np.where(rows[:, 0:2] == px, px - 1, rows[:, 0:2])   # (np.histogram2d: the last bin is closed on the right)
+        rows = self._grid_rows_to_metres(rows)
+        rows[:, 9] = 0
+        hf, self.height_filter = self.height_filter, None
+        try:
+            empty = np.zeros((0, 10))
+            _, p64, cnt = self.class_planes_device(rows, empty, empty, groups, np.eye(3), 0., 0., float(self.view_size),
+                                                   want_counts=True)
+        finally:
+            self.height_filter = hf
+        return p64[0].cpu().numpy(), cnt[0].cpu().numpy().view(np.uint32)
+
+    def gen_sem_probmap(self, pc: np.array, sem_clss: list):
+        """Dirichlet expectation of the classes `sem_clss` (sem_idxs names; integer classes are taken too) per cell of
+        pre-gridded rows: f64 (px, px), image rows, as bev_generator.py:373-394 of the reference returns it."""
+        return self._class_counts_from_grid_rows(pc, [self._classes_of(sem_clss)])[0][0]
+
+    def gen_gridmap_count_map(self, pc: np.array, weights: np.array = None) -> np.array:
+        """Points per cell of pre-gridded rows, f64 (px, px), image rows (bev_generator.py:438-455 of the reference).  With
+        `weights` the sums are a host np.bincount over the same cell indices: not a hot path -- the reference itself uses
+        it for per-class intensity sums only, which this drop-in gets from the rasteriser."""
+        px = self.pixel_size
+        if weights is None:
+            return self._class_counts_from_grid_rows(pc, [[]])[1][1].astype(np.float64)
+        pc = np.asarray(pc)
+        i, j = np.floor(pc[:, 0]).astype(np.int64), np.floor(pc[:, 1]).astype(np.int64)
+        i[pc[:, 0] == px] = px - 1                   # (np.histogram2d: the last bin is closed on the right)
+        j[pc[:, 1] == px] = px - 1
+        ok = (i >= 0) & (i < px) & (j >= 0) & (j < px)
+        flat = np.bincount((px - 1 - j[ok]) * px + i[ok], weights=np.asarray(weights, dtype=np.float64)[ok],
+                           minlength=px * px)
+        return flat.reshape(px, px)
 
     def to_host_async(self, planes, results):
         """planes: cuda float16 [k,21,px,px] holding the k device_only results `results` (generate(..., device_only=True,

@@ -363,7 +363,7 @@ class Kitti360SemanticPointCloudAccumulator(SemanticPointCloudAccumulator):
     def _fast_bev_ok(self, present_idx):
         gen = self.sem_bev_generator
         if not self._fast or type(gen) is not _mods()[4] or gen.do_aug or gen.do_warp or self._store is None \
-                or getattr(self._track, '_h', None) is None or os.environ.get('PCA_SYNC_BEV'):
+                or getattr(self._track, '_h', None) is None or os.environ.get('PCA_SYNC_BEV') or getattr(gen, 'sem_planes', None):
             return False
         if not isinstance(present_idx, (int, np.integer)):
             return False

@@ -53,6 +53,8 @@ class DeviceStore:
         self._ws = None
         self._ws_many = None
         self._ws_points, self._ws_px = 0, 0
+        self._ws_cls = None      # scratch of bev_class_planes, its own (a main raster may have sized _ws differently)
+        self._ws_cls_points, self._ws_cls_px = 0, 0
         self._dedup_ws = None
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
@@ -590,6 +592,40 @@ class DeviceStore:
         if self._pending and write_back:
             self._pending = []
         self._k1_noted = None                      # (a raster takes a noted K1 along or runs it first: nothing is noted any more)
+
+    def bev_class_planes(self, split_frame, prm, groups, first_frame=0, last_frame=None, want_counts=False):
+        """Planes of any semantic class groups over live frames [first_frame, last_frame), 'present' = frames before
+        split_frame (pca_bev_class_planes: one counts-only pass for all groups).  groups: a list of class-index lists (1..16
+        of them, they may overlap).  Returns (prob_f16, prob_f64, counts | None) as cuda tensors: [3, len(groups), px, px]
+        float16 / float64 and -- want_counts -- [3, len(groups) + 1, px, px] int32 holding the u32 counts per group, the last
+        slot every static point; set order {present, future, full}.  The store is not written: owed re-transforms are applied
+        to what the call reads and stay owed."""
+        ctx, lib = self.ctx, self.ctx.lib
+        self.flush_k1()
+        last_frame = self.n_frames if last_frame is None else last_frame
+        px, ng = int(prm.px), len(groups)
+        cg = (_lib.PcaClassGroup * max(ng, 1))()
+        for k, g in enumerate(groups):
+            cg[k].mask[:] = list(_lib.class_mask(g))
+        # the owed chain, read only (bev_pending flushes it when this raster does not cover what is owed)
+        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+        max_points = self.max_window_points()
+        if self._ws_cls is None or max_points > self._ws_cls_points or px != self._ws_cls_px:
+            self._ws_cls_points, self._ws_cls_px = int(max_points * 1.25) + 1, px
+            need = lib.pca_bev_class_workspace_bytes(self._ws_cls_points, px)
+            if self._ws_cls is None or self._ws_cls.numel() < need:
+                self._ws_cls = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        shape = (3, max(ng, 1), max(px, 1), max(px, 1))
+        p16 = torch.empty(shape, dtype=torch.float16, device=self.device)
+        p64 = torch.empty(shape, dtype=torch.float64, device=self.device)
+        cnt = torch.empty((3, shape[1] + 1) + shape[2:], dtype=torch.int32, device=self.device) if want_counts else None
+        st = self.c_store()
+        ctx.check(lib.pca_bev_class_planes(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
+                                           self.head + split_frame, self.head + last_frame, max_points, C.byref(prm), cg, ng,
+                                           pend_T, pend_ends, n_pend, self._ws_cls.data_ptr(), self._ws_cls.numel(),
+                                           p64.data_ptr(), p16.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                                           ctx.stream()))
+        return p16, p64, cnt
 
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters

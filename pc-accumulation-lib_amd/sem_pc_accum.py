@@ -57,6 +57,8 @@ class SemanticPointCloudAccumulator:
                 self.sem_idxs, bev_params['view_size'], bev_params['pixel_size'], bev_params['max_trans_radius'],
                 bev_params['zoom_thresh'], bev_params['do_warp'], bev_params['int_scaler'],
                 bev_params['int_sep_scaler'], bev_params['int_mid_threshold'], bev_params['height_filter'])
+            # extension: extra class planes per sample (SemBEVGenerator.sem_planes); the key is optional
+            self.sem_bev_generator.sem_planes = dict(bev_params.get('sem_planes') or {})
         elif bev_params['type'] == 'rgb':
             raise NotImplementedError('Needs refactoring')
 
@@ -304,7 +306,7 @@ class SemanticPointCloudAccumulator:
         gen = self.sem_bev_generator
         if self._store is not None:
             self._store.poll_status()
-        if not isinstance(pcs['pc_present'], WindowPart) or os.environ.get('PCA_SYNC_BEV'):
+        if not isinstance(pcs['pc_present'], WindowPart) or os.environ.get('PCA_SYNC_BEV') or getattr(gen, 'sem_planes', None):
             return [gen.generate_multiproc((pcs, self._copy_trajs(trajs)), worker=self._aug_worker0 + k)
                     for k in range(bev_num)]
         px = gen.pixel_size
@@ -329,6 +331,12 @@ class SemanticPointCloudAccumulator:
         if not present_idxs:
             return []
         self.store.poll_status()
+        if getattr(gen, 'sem_planes', None):      # class planes: sample by sample, plain dicts (the path PCA_SYNC_BEV=1 takes in _run_bev)
+            out = []
+            for idx in present_idxs:
+                pcs, trajs = self._window_inputs_for(idx, gen_future)
+                out.append(gen.generate_multiproc((pcs, self._copy_trajs(trajs))))
+            return out
         px = gen.pixel_size
         planes = torch.empty((len(present_idxs), 21, px, px), dtype=torch.float16, device=self.store.device)
         with gen.raster_batch():

@@ -1085,6 +1085,78 @@ def case_k1_edges(ref, out_dir):
         print(f'k1_edges_{name}: {n} points, {int(mask.sum())} in the image, {len(kept)} kept, {os.path.getsize(path)} bytes')
 
 
+def case_sem_planes(ref, out_dir):
+    """Class-group planes: the reference's gen_sem_probmap / gen_gridmap_count_map of the static partition for five class
+    groups and the three point sets (tests/golden/sem_planes.npz).  Augmented frame with a height filter; dyn = 1 rows, rows
+    above the filter, rows on the crop edge and a row one ulp inside +view/2 are part of the data."""
+    rng = np.random.default_rng(808)
+    view, px, hf = 20, 32, 1.5
+    rot, dx, dy, zoom = 0.7, 1.5, -2.25, 1.1
+    aug = zoom * view
+    gen = ref.SemBEVGenerator(SEM_IDXS, view, px, 0., 0., False, 20., 20., 0.5, hf)
+    gen.sem_idxs = {c: c for c in range(256)}          # groups are integer classes: the reference's own lookup, identity
+    groups = [[1], [13, 14, 15, 17], [0, 2, 8], [200, 201], [0, 255]]
+    classes = (0, 0, 0, 1, 1, 2, 8, 9, 13, 14, 15, 17, 5, 255)
+    R = gen.rotation_matrix_3d(rot)
+
+    def make(n):
+        rows = np.zeros((n, 10))
+        rows[:, :2] = rng.uniform(-14., 14., (n, 2))
+        rows[:, 2] = rng.integers(-8, 13, n) / 4.      # -2 .. 3: a quarter of them at or above the filter
+        rows[:, 3] = rng.integers(0, 65, n) / 64.
+        rows[:, 4:7] = rng.integers(0, 256, (n, 3))
+        rows[:, 7] = rng.choice(classes, n)
+        rows[:, 8] = rng.integers(-1, 4, n)
+        rows[:, 9] = (rng.random(n) < 0.1).astype(float)
+        # crop edges: ladders of neighbouring doubles around the points that land on +-view/2
+        vhi = 0.5 * aug
+        k = 0
+        for axis, target in ((0, vhi), (0, np.nextafter(vhi, -np.inf)), (0, -vhi), (1, vhi), (1, -vhi)):
+            t = np.array([0.3 * vhi, -0.2 * vhi])
+            t[axis] = target
+            xy = (t - [dx, dy]) @ R[:2, :2]
+            for step in range(-12, 13):
+                r = rows[k]
+                r[:2] = xy
+                for _ in range(abs(step)):
+                    r[axis] = np.nextafter(r[axis], np.inf if step > 0 else -np.inf)
+                r[2], r[7], r[9] = 0.25, classes[k % len(classes)], 0.
+                k += 1
+        return rows[rng.permutation(n)]
+
+    present, future = make(1500), make(1200)
+    sets = dict(present=present, future=future, full=np.concatenate([present, future]))
+    out = dict(pc_present=present, pc_future=future, cfg=np.array([view, px, hf, rot, dx, dy, zoom]),
+               groups=np.array([g + [-1] * (4 - len(g)) for g in groups], dtype=np.int16))
+    on_edge = inside = 0
+    for name, rows in sets.items():
+        xyz = np.matmul(R, rows[:, :3].copy().T).T      # (what geometric_transform computes, to count the edge rows)
+        tx = xyz[:, 0] + dx
+        on_edge += int((np.abs(tx) == 0.5 * aug).sum())
+        inside += int((tx == np.nextafter(0.5 * aug, -np.inf)).sum())
+        grid, _ = gen.preprocess_pc_and_trajs(rows.copy(), [], rot, dx, dy, aug)
+        assert (grid[:, 0:2] >= 0).all() and (grid[:, 0:2] <= px).all()
+        _, static = gen.partition_semantic_pc(grid, [1], 9)
+        if name != 'full':
+            out[f'grid_{name}'] = grid
+        prob = np.stack([gen.gen_sem_probmap(static, g) for g in groups])
+        out[f'prob_{name}'] = prob
+        out[f'prob16_{name}'] = prob.astype(np.float16)
+        out[f'count_{name}'] = gen.gen_gridmap_count_map(static)
+        for k, g in enumerate(groups):
+            sem, _ = gen.partition_semantic_pc(static, g, 7)
+            out[f'count_{name}_g{k}'] = gen.gen_gridmap_count_map(sem).astype(np.uint32)
+        assert name == 'full' or ((grid[:, 9] == 1).sum() > 20 and (rows[:, 2] >= hf).sum() > 100)
+    assert on_edge >= 4 and inside >= 1, (on_edge, inside)
+    assert (out['grid_present'][:, 0] == px).any() or (out['grid_future'][:, 0] == px).any()   # one ulp inside floors to px
+    assert out['count_full_g3'].sum() == 0 and out['count_full_g4'].sum() > 0
+    path = os.path.join(out_dir, 'sem_planes.npz')
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 200 * 1024, os.path.getsize(path)
+    print('sem_planes:', {k: v.shape[0] for k, v in sets.items()}, 'rows,', on_edge, 'on the crop edge,', inside,
+          'one ulp inside,', os.path.getsize(path), 'bytes')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(
@@ -1097,7 +1169,7 @@ def main():
     ref = import_reference()
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
                  bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
-                 utils=case_utils, sweeps=case_sweeps)
+                 utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
