@@ -166,6 +166,48 @@ int pca_nusc_project_cams(pca_ctx *ctx, const double *pc_lidar, int32_t n, const
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K0s NuScenes sweep merging + GT-box point labelling: the lidar sweeps of one sample into the keyframe's lidar frame,
+ *     points next to the sensor axis dropped, every point labelled with the track index and class of the LAST candidate
+ *     box of its own sweep that contains it.  Replaces the per-point part of inst_centric_get_sweeps,
+ *     datasets/nuscenes_utils.py:233-243, :312-329, :332-531 (the dataset walk and the per-track lists stay on the host).
+ *     raw: dev f32 [n_points][5], the sweeps' .bin rows concatenated oldest sweep first (column 4 is never read).
+ *     sweeps / boxes: HOST tables (they travel through the context's pinned block, fetched by a kernel); a sweep's boxes
+ *       are consecutive.  Limits: PCA_NUSC_MAX_SWEEPS sweeps, PCA_NUSC_MAX_SWEEP_BOXES boxes, PCA_NUSC_MAX_SWEEP_TILES tiles
+ *       of 512 points (a tile never straddles a sweep; every sweep has at least one); beyond them -1, the limit named by
+ *       pca_last_error, nothing launched.
+ *     Per point: keep = sqrt(x*x + y*y) > center_radius in un-fused f32; xyz' = f32(T . [x y z 1]) (f64 fma chain in k
+ *       order); per box: local = inv . [xyz' 1] (the same chain over the f32-rounded xyz'), inside iff
+ *       fabs(local[a] / size[a]) < inside_limit on the three axes (IEEE f64 division; NaN, inf, size 0: false).
+ *     points_out: dev f32 [<= n_points][8] rows x', y', z', intensity, lag, sweep, inst, cls of the kept points, in sweep
+ *       order then point order; inst = index of the box's track (a box opens a track iff it has a hit and no earlier box
+ *       of the same track_key has; tracks are numbered in box order), cls = the box's class, both -1 without a box.
+ *     tally_out: dev int32 [n_sweeps + 1 + n_boxes]: the kept rows before every sweep (and their total), then per box
+ *       the number of kept points of its sweep inside it.
+ *     workspace: dev, pca_nusc_merge_sweeps_workspace_bytes(n_points, n_boxes) bytes.  Two launches, no synchronisation.
+ *     PCA_NUSC_SWEEPS_PRETEST=0 turns the certified comparison that spares most divisions off (A/B; same results).
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_NUSC_MAX_SWEEPS 32
+#define PCA_NUSC_MAX_SWEEP_BOXES 4096
+#define PCA_NUSC_MAX_SWEEP_TILES 16384
+typedef struct {
+    int32_t row0, n_rows;      /* the sweep's rows of raw */
+    int32_t box0, n_boxes;     /* its candidate boxes */
+    float lag, sweep;          /* columns 4, 5 of its points */
+    double T[12];              /* rows 0..2 of target_from_sweep */
+} pca_nusc_sweep;
+typedef struct {
+    double inv[12];            /* rows 0..2 of inv(target_from_box) */
+    double size[3];            /* l, w, h */
+    int32_t cls;               /* class index */
+    int32_t track_key;         /* ordinal of the box's instance token among the call's candidates, 0 .. n_boxes - 1 */
+} pca_nusc_sweep_box;
+int64_t pca_nusc_merge_sweeps_workspace_bytes(int64_t n_points, int n_boxes);
+int pca_nusc_merge_sweeps(pca_ctx *ctx, const float *raw /*dev*/, int64_t n_points, const pca_nusc_sweep *sweeps,
+                          int n_sweeps, const pca_nusc_sweep_box *boxes, int n_boxes, float center_radius,
+                          double inside_limit, void *workspace /*dev*/, int64_t workspace_bytes,
+                          float *points_out /*dev*/, int32_t *tally_out /*dev*/, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K2  in-place rigid re-transform of every stored point of frames [slot_begin, slot_end).
  *     Replaces sem_pc_accum.py:167-183 (update_sem_pcs).  Ts: n_T 4x4 row-major matrices applied one
  *     after the other (n_T = 1 is the reference's per-step call; n_T > 1 applies a backlog of steps in

@@ -8,10 +8,13 @@ unchanged.  What runs where:
   * merging the lidar sweeps of a sample and labelling points with their GT boxes (the reference's
     `inst_centric_get_sweeps`, datasets/nuscenes_utils.py:332-531) is done by `NuScenesDataloader.sweep_provider`, a
     callable with that function's signature returning its dict; the default is this package's own
-    `datasets.nuscenes_sweeps.inst_centric_get_sweeps`.
+    `datasets.nuscenes_sweeps.inst_centric_get_sweeps` (numpy on the host); with PCA_NUSC_SWEEPS=device and no provider set,
+    its device form `inst_centric_get_sweeps_device` (kernel K0s, bit-identical).
 
 nuscenes-devkit / pyquaternion are only imported when a real dataset is walked.
 """
+import os
+
 import numpy as np
 
 from datasets.nuscenes_utils import NuScenesCamera, NuScenesLidar, project_to_cameras
@@ -46,8 +49,15 @@ class NuScenesDataloader(ObservationDataloader):
     def _sweeps(self, sample_token, cfg):
         if self.sweep_provider is not None:
             return self.sweep_provider(self.nusc, sample_token, **cfg)
+        if self.device_sweeps():
+            from datasets.nuscenes_sweeps import inst_centric_get_sweeps_device
+            return inst_centric_get_sweeps_device(self.nusc, sample_token, **cfg)
         from datasets.nuscenes_sweeps import inst_centric_get_sweeps
         return inst_centric_get_sweeps(self.nusc, sample_token, **cfg)
+
+    def device_sweeps(self):
+        """the opt-in device merge: no provider set and PCA_NUSC_SWEEPS=device"""
+        return self.sweep_provider is None and os.environ.get('PCA_NUSC_SWEEPS', '') == 'device'
 
     def _lidar(self, sample):
         return NuScenesLidar(self.nusc, self.nusc.get('sample_data', sample['data']['LIDAR_TOP']))
@@ -56,10 +66,13 @@ class NuScenesDataloader(ObservationDataloader):
         return [NuScenesCamera(self.nusc, self.nusc.get('sample_data', sample['data'][ch])) for ch in self.cam_channels]
 
     # ---- one observation -------------------------------------------------------------------------------------
-    def read_host(self, idx):
+    def read_host(self, idx, defer_sweeps=False):
         """Everything of one observation that needs no GPU: sample records, the merged sweeps, sensor poses and intrinsics,
         the camera images (as the sensor objects hold them).  `finish_obs` turns it into the reference's observation; the
-        ingest pipeline (pca_amd.ingest.NuScenesPrefetchingLoader) runs this part on reader threads, ahead of the GPU."""
+        ingest pipeline (pca_amd.ingest.NuScenesPrefetchingLoader) runs this part on reader threads, ahead of the GPU.
+        With defer_sweeps (the pipeline in device mode) only the host part of the merge is done here -- geom['sweeps'] holds
+        `collect_sweep_inputs`' result and the merge's settings, geom['pc'] is None -- and the caller merges on the device
+        and calls `fill_instances`."""
         sample_token = self.sample_tokens[idx]
         sample = self.nusc.get('sample', sample_token)
         obs = {'meta': {'sample_token': sample_token, 'scene_token': sample['scene_token'],
@@ -74,23 +87,35 @@ class NuScenesDataloader(ObservationDataloader):
                                   'pedestrian'),
             'map_point_feat2idx': {'sweep_idx': self.sweep_idx, 'inst_idx': self.inst_idx, 'cls_idx': self.cls_idx},
         }
-        out = self._sweeps(sample_token, cfg)
+        if defer_sweeps:
+            from datasets.nuscenes_sweeps import collect_sweep_inputs
+            out = {'points': None, 'instances_token': None, 'instances_name': (), 'instances_center': None}
+            deferred = (collect_sweep_inputs(self.nusc, sample_token, cfg['n_sweeps'], cfg['detection_classes']), cfg)
+        else:
+            out = self._sweeps(sample_token, cfg)
         lidar = self._lidar(sample)
         cameras = self._cameras(sample)
         obs['ego_at_lidar_ts'] = lidar.glob_from_ego
         obs['images'] = [cam.img for cam in cameras]
-        obs['inst_tokens'] = out['instances_token']
-        obs['inst_cls'] = [int(cls.item()) for cls in out['instances_name']]
-        obs['inst_center'] = out['instances_center']
+        self.fill_instances(obs, out['instances_token'], out['instances_name'], out['instances_center'])
         sd = self.nusc.get('sample_data', sample['data']['LIDAR_TOP'])
         x, y, _ = self.nusc.get('ego_pose', sd['ego_pose_token'])['translation']
         obs['ego_global_x'] = x
         obs['ego_global_y'] = y
-        geom = dict(pc=np.asarray(out['points']),               # lidar frame, (N, >= 7) sweep matrix
+        geom = dict(pc=None if defer_sweeps else np.asarray(out['points']),     # lidar frame, (N, >= 7) sweep matrix
                     ego_from_lidar=lidar.ego_from_self, glob_from_ego=lidar.glob_from_ego,
                     cams_glob_from_self=[cam.glob_from_self for cam in cameras], cams_K=[cam.cam_K for cam in cameras],
                     cams_wh=[cam.img_wh for cam in cameras])
+        if defer_sweeps:
+            geom['sweeps'] = deferred
         return obs, geom
+
+    @staticmethod
+    def fill_instances(obs, tokens, names, centres):
+        """the three per-instance entries of an observation from a merge's result (names: class index per track)"""
+        obs['inst_tokens'] = tokens
+        obs['inst_cls'] = [int(cls.item()) for cls in names]
+        obs['inst_center'] = centres
 
     def finish_obs(self, obs, geom):
         """Projection onto the cameras (K0n on the device) and the (N,7) point rows, as host arrays."""

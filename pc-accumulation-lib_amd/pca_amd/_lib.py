@@ -19,7 +19,8 @@ SAMPLE_MODES = {'nearest': 0, 'bilinear': 1}
 
 EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error', 'pca_status', 'pca_status_peek', 'pca_status_mirror',
            'pca_kitti_project_sample_filter', 'pca_kitti_project_sample_filter_ex',
-           'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams', 'pca_retransform', 'pca_retransform_batch_tail',
+           'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
+           'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
            'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_warp', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
@@ -161,6 +162,10 @@ def load():
         vp, vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
         C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp, vp, vp, vp
     ]
+    lib.pca_nusc_merge_sweeps_workspace_bytes.argtypes = [i64, i32]
+    lib.pca_nusc_merge_sweeps_workspace_bytes.restype = i64
+    # (sweeps / boxes: addresses of numpy record arrays laid out like pca_nusc_sweep / pca_nusc_sweep_box)
+    lib.pca_nusc_merge_sweeps.argtypes = [vp, vp, i64, vp, i32, vp, i32, C.c_float, C.c_double, vp, i64, vp, vp, vp]
     lib.pca_retransform.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, C.POINTER(C.c_double), i32, vp]
     lib.pca_retransform_batch_tail.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, C.POINTER(C.c_double), vp]
     lib.pca_mark_dynamic.argtypes = [vp, C.POINTER(PcaStore), vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp]

@@ -354,7 +354,12 @@ class NuScenesPrefetchingLoader:
     order.  The consumer's thread (the only one that talks to HIP) stages the six decoded images into ONE pinned block (the
     host copies side by side on the staging pool) and enqueues one 26 MB H2D copy instead of a pageable, blocking
     `.to(device)` of an `np.stack`; the lidar points go up once, K0n projects them on the device and the (N,7) rows the
-    accumulator takes are assembled there -- nothing of the observation comes back to the host."""
+    accumulator takes are assembled there -- nothing of the observation comes back to the host.
+    Device mode of the sweep merge (PCA_NUSC_SWEEPS=device, no sweep_provider): the reader threads only run
+    `collect_sweep_inputs` (no HIP call); the consumer's thread stages the raw f32 rows of the sweeps through the pinned ring,
+    runs the merge (K0s) with the points left on the device, stages the images behind it, waits once for the hit counts (from
+    which `inst_tokens` / `inst_cls` / `inst_center` follow) and feeds K0n from the device points -- the merged points never
+    visit the host."""
 
     RING = 64                                # batches: a whole scene (~40 samples) can be collected and integrated at once
 
@@ -395,7 +400,12 @@ class NuScenesPrefetchingLoader:
         return pin[:n].view(*shape)
 
     def _host_part(self, idx):
-        obs, geom = self.loader.read_host(idx)
+        # device mode of the sweep merge (PCA_NUSC_SWEEPS=device): reader threads only collect the merge's host inputs
+        device_sweeps = getattr(self.loader, 'device_sweeps', None)
+        if device_sweeps is not None and device_sweeps():
+            obs, geom = self.loader.read_host(idx, defer_sweeps=True)
+        else:
+            obs, geom = self.loader.read_host(idx)
         imgs = [np.asarray(im, dtype=np.uint8) if not isinstance(im, str) else im for im in obs['images']]   # decode here
         return obs, geom, imgs
 
@@ -411,12 +421,35 @@ class NuScenesPrefetchingLoader:
         if pslot['copied'] is not None:
             pslot['copied'].synchronize()                  # the copies out of this pinned block, a few uploads ago
         lib, ctx = self.ctx.lib, self.ctx
-        pc = np.ascontiguousarray(geom['pc'], dtype=np.float64)
-        n, ncam = pc.shape[0], len(geom['cams_K'])
-        pin_pc, dev_pc = self._pin_buffer(pslot, 'pc', pc.shape, torch.float64), self._dev_buffer(slot, 'pc', pc.shape, torch.float64)
+        ncam = len(geom['cams_K'])
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def stage(src, pin, dev, nbytes):                    # pinned copies on the library's staging threads, H2D enqueued
+            vp = C.c_void_p * len(src)
+            if lib.pca_host_stage_h2d(len(src), vp(*src), vp(*pin), vp(*dev), (C.c_int64 * len(src))(*nbytes), stream) != 0:
+                raise RuntimeError('pca_host_stage_h2d failed')
+
+        src, pin, dev, nbytes = [], [], [], []
+        merge = None
+        if geom.get('sweeps') is not None:
+            # the merge on the device: the raw f32 rows of the sweeps go up through the pinned ring, the launches and the
+            # tally's read-back are enqueued, and the images are staged behind them before the (one) wait
+            from datasets import nuscenes_sweeps as ns
+            inputs, cfg = geom['sweeps']
+            tables = ns.sweep_tables(inputs)
+            raw = tables[0]
+            pin_raw = self._pin_buffer(pslot, 'raw', raw.shape, torch.float32)
+            dev_raw = self._dev_buffer(slot, 'raw', raw.shape, torch.float32)
+            if raw.shape[0]:
+                stage([raw.ctypes.data], [pin_raw.data_ptr()], [dev_raw.data_ptr()], [raw.nbytes])
+            merge, keep_alive = ns.merge_sweeps_launch(inputs, cfg['center_radius'], cfg['in_box_tolerance'], device_points=True,
+                                                       raw_dev=dev_raw, tables=tables)
+        else:
+            pc = np.ascontiguousarray(geom['pc'], dtype=np.float64)
+            pin_pc, dev_pc = self._pin_buffer(pslot, 'pc', pc.shape, torch.float64), self._dev_buffer(slot, 'pc', pc.shape, torch.float64)
+            src, pin, dev, nbytes = [pc.ctypes.data], [pin_pc.data_ptr()], [dev_pc.data_ptr()], [pc.nbytes]
         images = obs['images']
         real = all(isinstance(im, np.ndarray) and im.ndim == 3 for im in imgs) and len({im.shape for im in imgs}) == 1
-        src, pin, dev, nbytes = [pc.ctypes.data], [pin_pc.data_ptr()], [dev_pc.data_ptr()], [pc.nbytes]
         if real:
             ishape = (len(imgs), ) + imgs[0].shape
             pin_im, dev_im = self._pin_buffer(pslot, 'img', ishape, torch.uint8), self._dev_buffer(slot, 'img', ishape, torch.uint8)
@@ -425,16 +458,22 @@ class NuScenesPrefetchingLoader:
             for k, im in enumerate(imgs):
                 src.append(im.ctypes.data); pin.append(pin_im.data_ptr() + k * each)
                 dev.append(dev_im.data_ptr() + k * each); nbytes.append(each)
-        import ctypes as C                                   # pinned copies on the library's staging threads, H2D enqueued
-        vp = C.c_void_p * len(src)
-        if lib.pca_host_stage_h2d(len(src), vp(*src), vp(*pin), vp(*dev), (C.c_int64 * len(src))(*nbytes),
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
-            raise RuntimeError('pca_host_stage_h2d failed')
+        if src:
+            stage(src, pin, dev, nbytes)
         if real:
             images = DeviceImages(obs['images'], dev_im)
         ev = torch.cuda.Event()
         ev.record()
         pslot['copied'] = ev
+        if merge is not None:
+            res = merge.finish()                             # the wait; the merged points stay on the device
+            del keep_alive
+            obs = dict(obs)
+            self.loader.fill_instances(obs, res['instances_token'], np.array([tr['cls'] for tr in res['tracks']], np.float32),
+                                       res['instances_center'])
+            dev_pc = self._dev_buffer(slot, 'pc', tuple(res['points'].shape), torch.float64)
+            dev_pc.copy_(res['points'])                      # f32 -> f64 is exact
+        n = dev_pc.shape[0]
         # projection (K0n) on the device, rows [x, y, z (ego), intensity, u, v, instance] assembled there
         xyz = dev_pc[:, :3].contiguous()
         ego = self._dev_buffer(slot, 'ego', (n, 3), torch.float64)

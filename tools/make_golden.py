@@ -1050,6 +1050,41 @@ def case_sweeps(ref, out_dir):
     print('nusc_sweeps written:', out['points'].shape, len(res['instances_token']), 'labelled boxes')
 
 
+def case_sweeps_edges(ref, out_dir):
+    """The reference's inst_centric_get_sweeps + load_data_to_tensor on the scenarios of tests/nusc_sweeps_edges_common.py
+    (points on box faces and on the radius circle with their f32 neighbours; empty file, sweep without box, tile-sized
+    sweeps, overlapping boxes, a track opened by a later box): the tables and the recorded outputs, per scenario."""
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import fake_nuscenes as fk
+    import nusc_sweeps_edges_common as ec
+    ref.nu.Quaternion = fk.FakeQuaternion          # pyquaternion stand-in (textbook formula; third-party, unpinned)
+    out = {}
+    for name in sorted(ec.SCENARIOS):
+        tables = ec.TABLES[name]()
+        with tempfile.TemporaryDirectory() as tmp:
+            nusc = fk.FakeNuScenes(tables, tmp)
+            res = ref.nu.inst_centric_get_sweeps(nusc, 'sample0', **ec.cfg(name))
+            ref.nu.load_data_to_tensor(res)
+        ec.store_tables(out, name, tables)
+        out[name + '_points'] = res['points'].numpy()
+        out[name + '_instances_token'] = np.array(res['instances_token'])
+        out[name + '_instances_center'] = np.stack(res['instances_center'])
+        out[name + '_instances_last_box'] = res['instances_last_box'].numpy()
+        out[name + '_instances_name'] = res['instances_name'].numpy()
+        print('nusc_sweeps_edges', name, out[name + '_points'].shape, list(res['instances_token']))
+    print('  scenario a (face labelled, face unlabelled, circle kept, circle dropped) per record:',
+          ec.coverage_a(ec.TABLES['a'](), out['a_points']))
+    pb = out['b_points']
+    assert [int((pb[:, 5] == k).sum()) for k in range(4)] == list(ec.KEPT_B)
+    toks = list(out['b_instances_token'])
+    assert toks.count('inst2') == 1 and 'inst6' in toks and 'inst0' in toks
+    path = os.path.join(out_dir, 'nusc_sweeps_edges.npz')
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 400 * 1000, os.path.getsize(path)
+    print('nusc_sweeps_edges written:', os.path.getsize(path), 'bytes')
+
+
 def case_k1_edges(ref, out_dir):
     """The reference's velo2img / gen_semantic_pc / filter_semseg_pc on the frames of tests/k1_edges_common.py (points at the
     frustum's planes and their f32 neighbours, a ladder of magnitudes up to FLT_MAX, special values): one file per camera with
@@ -1169,7 +1204,8 @@ def main():
     ref = import_reference()
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
                  bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
-                 utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes)
+                 utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes,
+                 sweeps_edges=case_sweeps_edges)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
