@@ -380,6 +380,42 @@ int pca_bev_class_planes(pca_ctx *ctx, const pca_store *store, const int64_t *fr
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The BEV window partitioned by height above the cell minimum.  Replaces
+ *       bev_generator/sem_bev.py:556-591 (static_obj_partitioning_by_elev: the per-cell minimum-z map of the rows it is
+ *       given, then every row whose z lies more than elev_thresh above its cell's minimum is flagged; two per-point Python
+ *       loops), and the geometry of bev_generator/bev_generator.py:127-160, :207-255, :737-747 exactly as the rasteriser
+ *       above evaluates it (owed re-transforms oldest first, origin, R, dx / dy, strict crop, z < height_filter, floor to
+ *       the grid, clamp, image rows; a point whose z is not finite is dropped).
+ *     include_dyn == 0: points with dyn == 1 are dropped (the static partition generate_bev uses, sem_bev.py:57-69);
+ *       include_dyn != 0: they take part (the reference's method never looks at dyn).
+ *     A point's z is (Z - origin z) + 0.0 in f64: -0.0 arrives as +0.0, as the reference's np.matmul delivers it.
+ *     elevated = z > (min z of the cell + elev_thresh): an f64 add and a strict f64 compare.  elev_thresh may be negative
+ *       (the reference accepts it); NaN is refused.
+ *     Output (dev, any of them may be NULL, not all): elev f64 [px][px] (the cell minimum, 0.0 where no point), observed u8
+ *       [px][px] (0 / 1), flags u8 [window points] in window order (0 kept, 1 elevated, 255 not in view; every byte of the
+ *       window is written exactly once, the caller need not clear it), counts int64 [3] {in view, elevated, not elevated}.
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
+ *     Grid: 1 <= px <= 1024 (else "bev elev partition: px must be in 1..1024": no banding).
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to what is read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a bin range
+ *     armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared (the whole window is read).  A window above
+ *     max_points is cut there and raises PCA_STATUS_STORE_OVERFLOW (flags beyond the cut are not written); a window without
+ *     points gives elev 0, observed 0 and counts 0.  The window index must fit 32 bits.
+ *     Every argument is checked before anything is launched; -1 with pca_last_error set.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t pca_bev_elev_workspace_bytes(int64_t max_points, int px);
+int pca_bev_elev_partition(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                           int slot_begin, int slot_end, int64_t max_points,
+                           const pca_bev_params *prm, double elev_thresh, int include_dyn,
+                           const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                           void *workspace /*dev*/, int64_t workspace_bytes,
+                           double *elev      /*dev [px][px]         or NULL*/,
+                           uint8_t *observed /*dev [px][px]         or NULL*/,
+                           uint8_t *flags    /*dev [window points]  or NULL: 0 kept, 1 elevated, 255 not in view*/,
+                           int64_t *counts   /*dev [3]: in view, elevated, not elevated; or NULL*/,
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -573,7 +609,7 @@ int64_t pca_host_track_trigger(pca_host_track *t, double bev_horizon, int64_t pr
 enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
     PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
-    PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_COUNT
+    PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

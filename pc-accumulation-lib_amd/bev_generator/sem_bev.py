@@ -266,6 +266,57 @@ class SemBEVGenerator(BEVGenerator):
                            minlength=px * px)
         return flat.reshape(px, px)
 
+    # ---- partition by height above the cell minimum (extension: pca_bev_elev_partition) ------------
+    def elev_partition_device(self, pc, rot_mat, dx, dy, aug_view_size, elev_thresh, include_dyn=False, mark_dyn=False):
+        """One point set partitioned by height above its cells' minimum z, in the frame the 21 planes are rasterised in
+        (DeviceStore.bev_elev_partition: the dict of cuda tensors 'elev', 'observed', 'flags', 'counts').  pc: a WindowPart
+        (flags in the order of the part's frames in the store) or host rows in BEV-frame metres (flags in row order).
+        mark_dyn applies to a WindowPart only: the elevated points of the device window get dyn = 1, for good."""
+        if isinstance(pc, WindowPart):
+            w = pc.window
+            lo, hi = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
+            if w.future_is_present:
+                lo, hi = w.first, w.last
+            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
+            return w.store.bev_elev_partition(prm, elev_thresh, first_frame=lo, last_frame=hi, include_dyn=include_dyn,
+                                              mark_dyn=mark_dyn)
+        if mark_dyn:
+            raise ValueError('mark_dyn needs a device window: host rows are not written')
+        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
+        st = self._tmp_store('elev')
+        st.load_rows([pc])
+        return st.bev_elev_partition(prm, elev_thresh, include_dyn=include_dyn)
+
+    def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
+        """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the
+        partition column).  Builds the minimum-z map of ALL the rows (no static partition, no height filter: the method
+        reduces whatever rows it is given), sets column 8 of every row whose z lies more than elev_thresh above its cell's
+        minimum to 1 IN PLACE and returns (pc_static, pc_dynamic, elevmap, elevmap_obs_mask): the rows whose column 8 is 0,
+        those whose column 8 is 1 (a row whose column 8 was already >= 2 and is not elevated lands in neither), the f64
+        (px, px) minimum map in image rows and its bool mask.  Minimum and flags come from the device
+        (pca_bev_elev_partition); the bookkeeping runs on the caller's own f64 rows.
+        What differs from the reference, at inputs of measure zero: a cell index equal to px is clamped to px - 1 (the
+        reference raises an IndexError for column 0 and wraps to the last image row for column 1); where a pre-gridded z of
+        -0.0 ties with +0.0 for a cell's minimum, the map holds +0.0 (in the reference it holds whichever came first);
+        a row whose z is not finite, or whose cell lies outside the grid, takes no part and keeps its column 8."""
+        px = self.pixel_size
+        n = int(pc.shape[0])
+        rows = np.zeros((n, 10))
+        ij = np.asarray(pc[:, 0:2], dtype=np.float64)
+        rows[:, 0:2] = np.where(ij == px, px - 1, ij)
+        rows[:, 2] = pc[:, 2]
+        rows = self._grid_rows_to_metres(rows)
+        hf, self.height_filter = self.height_filter, None
+        try:
+            out = self.elev_partition_device(rows, np.eye(3), 0., 0., float(self.view_size), elev_thresh, include_dyn=True)
+        finally:
+            self.height_filter = hf
+        elevated = out['flags'].cpu().numpy() == 1
+        pc[elevated, 8] = 1
+        pc_static = pc[pc[:, 8] == 0]
+        pc_dynamic = pc[pc[:, 8] == 1]
+        return pc_static, pc_dynamic, out['elev'].cpu().numpy(), out['observed'].cpu().numpy()
+
     def to_host_async(self, planes, results):
         """planes: cuda float16 [k,21,px,px] holding the k device_only results `results` (generate(..., device_only=True,
         out=planes[i])).  ONE device->host copy of all k samples is enqueued on a side stream into pinned memory; returns

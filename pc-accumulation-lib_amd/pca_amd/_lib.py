@@ -22,7 +22,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
            'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
-           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_warp', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
+           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_warp', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
            'pca_host_track_poses', 'pca_host_track_segments', 'pca_host_track_set', 'pca_host_track_transform',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
@@ -31,7 +31,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_profile_enable', 'pca_profile_read')
 
 KERNEL_IDS = ('kitti_project_sample_filter', 'nusc_sample_filter_transform', 'nusc_project_cams', 'retransform',
-              'mark_dynamic', 'bev_bin', 'bev_scan', 'bev_scatter', 'bev_cells', 'bev_cells_heavy', 'voxel_dedup', 'bev_unit', 'icp', 'bev_class_bin', 'bev_class_cells')
+              'mark_dynamic', 'bev_bin', 'bev_scan', 'bev_scatter', 'bev_cells', 'bev_cells_heavy', 'voxel_dedup', 'bev_unit', 'icp', 'bev_class_bin', 'bev_class_cells', 'bev_elev_bin', 'bev_elev_cells')
 BEV_EXTRA_PLANES = ('elevation_max', 'elevation_mean', 'intensity_mean')
 
 
@@ -187,6 +187,10 @@ def load():
     lib.pca_bev_class_workspace_bytes.restype = i64
     lib.pca_bev_class_planes.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, i32, i64, C.POINTER(PcaBevParams),
                                          C.POINTER(PcaClassGroup), i32, vp, vp, i32, vp, i64, vp, vp, vp, vp]
+    lib.pca_bev_elev_workspace_bytes.argtypes = [i64, i32]
+    lib.pca_bev_elev_workspace_bytes.restype = i64
+    lib.pca_bev_elev_partition.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, i64, C.POINTER(PcaBevParams), C.c_double, i32,
+                                           vp, vp, i32, vp, i64, vp, vp, vp, vp, vp]
     lib.pca_bev_warp.argtypes = [vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.pca_voxel_dedup_workspace_bytes.restype = C.c_int64
     lib.pca_voxel_dedup_workspace_bytes.argtypes = [i64, i32]

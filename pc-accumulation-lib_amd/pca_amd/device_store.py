@@ -55,6 +55,8 @@ class DeviceStore:
         self._ws_points, self._ws_px = 0, 0
         self._ws_cls = None      # scratch of bev_class_planes, its own (a main raster may have sized _ws differently)
         self._ws_cls_points, self._ws_cls_px = 0, 0
+        self._ws_elev = None     # scratch of bev_elev_partition, its own for the same reason
+        self._ws_elev_points, self._ws_elev_px = 0, 0
         self._dedup_ws = None
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
@@ -626,6 +628,54 @@ class DeviceStore:
                                            p64.data_ptr(), p16.data_ptr(), None if cnt is None else cnt.data_ptr(),
                                            ctx.stream()))
         return p16, p64, cnt
+
+    def bev_elev_partition(self, prm, elev_thresh, first_frame=0, last_frame=None, include_dyn=False, mark_dyn=False,
+                           max_points=None):
+        """Live frames [first_frame, last_frame) partitioned by height above the cell minimum (pca_bev_elev_partition; the
+        reference's static_obj_partitioning_by_elev, sem_bev.py:556-591, in the frame of `prm`): a point is ELEVATED if its z
+        in the BEV frame lies more than elev_thresh (it may be negative) above the minimum z of its cell.  include_dyn=False:
+        points with dyn == 1 take no part (the static partition of generate_bev); True: every point does.
+        Returns a dict of cuda tensors: 'elev' float64 (px, px), the cell minimum (0 where nothing was seen), image rows;
+        'observed' bool (px, px); 'flags' uint8, one per point of the window in store order (0 kept, 1 elevated, 255 not in
+        view); 'counts' int64 [3] = points in view, elevated, not elevated.  (The length of 'flags' is the window's exact
+        point count: one offset is read back, the call synchronises.)
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed -- unless mark_dyn=True,
+        the only path that alters the store: the elevated points get dyn = 1 (owed re-transforms are flushed first).  The
+        mark is made in THIS view's cells and persists: every later raster, of any view, treats these points as dynamic.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        ctx, lib = self.ctx, self.ctx.lib
+        last_frame = self.n_frames if last_frame is None else last_frame
+        px = int(prm.px)
+        if mark_dyn:
+            self.flush_pending()                       # a call that must write: nothing stays owed
+        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
+        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+        bound = self.max_window_points()
+        max_points = bound if max_points is None else max(int(max_points), 1)
+        if self._ws_elev is None or max_points > self._ws_elev_points or px != self._ws_elev_px:
+            # sized with headroom so that a window growing frame by frame does not reallocate every call
+            self._ws_elev_points, self._ws_elev_px = int(max_points * 1.25) + 1, px
+        need = lib.pca_bev_elev_workspace_bytes(self._ws_elev_points, px)      # (asked every call: PCA_BEV_ELEV_G changes it)
+        if self._ws_elev is None or self._ws_elev.numel() < need:
+            self._ws_elev = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        side = max(px, 1)
+        elev = torch.empty((side, side), dtype=torch.float64, device=self.device)
+        obs = torch.empty((side, side), dtype=torch.uint8, device=self.device)
+        flags = torch.empty(max_points, dtype=torch.uint8, device=self.device)
+        counts = torch.empty(3, dtype=torch.int64, device=self.device)
+        st = self.c_store()
+        ctx.check(lib.pca_bev_elev_partition(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
+                                             self.head + last_frame, max_points, C.byref(prm), float(elev_thresh),
+                                             1 if include_dyn else 0, pend_T, pend_ends, n_pend, self._ws_elev.data_ptr(),
+                                             self._ws_elev.numel(), elev.data_ptr(), obs.data_ptr(), flags.data_ptr(),
+                                             counts.data_ptr(), ctx.stream()))
+        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
+        lo, n = int(lo_hi[0]), min(int(lo_hi[1] - lo_hi[0]), max_points)
+        flags = flags[:n]
+        if mark_dyn:
+            self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
+        return {'elev': elev, 'observed': obs.bool(), 'flags': flags, 'counts': counts}
 
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters

@@ -320,6 +320,23 @@ class SemanticPointCloudAccumulator:
         """(pcs, trajs) of one sample as generate_bev builds them (overridden where other agents' trajectories exist)."""
         return self._window_inputs(present_idx, gen_future)
 
+    def partition_by_elev(self, present_idx, elev_thresh, part='full', mark_dyn=False):
+        """Extension (the reference's static_obj_partitioning_by_elev, sem_bev.py:556-591, on the device window): the points
+        of `part` ('present' | 'future' | 'full') of the sample generate_bev(present_idx, 1, True) would make, partitioned by
+        height above the minimum z of their cell, in that sample's un-augmented frame (heading from the last two present
+        poses, no shift, zoom 1) and over its static partition (dyn != 1).  Returns DeviceStore.bev_elev_partition's dict of
+        cuda tensors; 'elev' of part='present' is the f64 elevation plane of that sample.  What KITTI needs, where no
+        instance labels exist and dyn is 0 everywhere: mark_dyn=True sets dyn = 1 for the elevated points, in the store,
+        for good -- they then stay out of the medians, the elevation and the intensity planes of every later sample."""
+        if part not in ('present', 'future', 'full'):
+            raise ValueError("part must be 'present', 'future' or 'full'")
+        gen = self.sem_bev_generator
+        self.store.poll_status()
+        pcs, trajs = self._window_inputs_for(present_idx, True)
+        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
+        return gen.elev_partition_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, elev_thresh,
+                                         include_dyn=False, mark_dyn=mark_dyn)
+
     def generate_bev_many(self, present_idxs, gen_future: bool = True):
         """Extension (no reference counterpart): the samples generate_bev(idx, 1, gen_future)[0] would return for every idx of
         `present_idxs`, rasterised in ONE launch of each kernel (the store does not change between them: the driver's sweep

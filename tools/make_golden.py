@@ -1192,6 +1192,122 @@ def case_sem_planes(ref, out_dir):
           'one ulp inside,', os.path.getsize(path), 'bytes')
 
 
+def case_elev_partition(ref, out_dir):
+    """The reference's static_obj_partitioning_by_elev (sem_bev.py:556-591) on a three-frame window, behind its own
+    preprocess_pc_and_trajs and -- for the static-only cases -- partition_semantic_pc: tests/golden/elev_partition.npz.
+    Thresholds 0.2, 0.0 and -0.1, with and without a height filter, with and without the dyn == 1 rows; variant 'z0' has
+    origin z = 0 (stored z of -0.0).  Column 3 of every row is its index in the window.  Reserved cells hold hand-made rows
+    only: a minimum m, a row at fl(m + 0.2) and its two neighbours; single rows; the -0.0 rows.  See the case list and the
+    names in tests/elev_partition_common.py."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import elev_partition_common as ec
+    rng = np.random.default_rng(556)
+    view, px, hf = 10, 20, 1.5
+    rot, dx, dy = 0.3, 0.15, -0.1
+    origins = dict(a=np.array([3.25, -1.5, 0.6]), z0=np.array([3.25, -1.5, 0.0]))
+    oz = origins['a'][2]
+    R = ec.rotation(rot)
+    frames = [[], [], []]
+
+    def add(f, i, j, Z, c8=0., dyn=0., jitter=0.3):
+        t = (np.array([i, j]) + 0.5 + rng.uniform(-jitter, jitter, 2) - 0.5 * px) * view / px
+        xy = (t - [dx, dy]) @ R[:2, :2] + origins['a'][:2]
+        row = np.zeros(10)
+        row[0:2], row[2] = xy, Z
+        row[4:7], row[7] = rng.integers(0, 256, 3), rng.integers(0, 19)
+        row[8], row[9] = c8, dyn
+        frames[f].append(row)
+
+    def stored_z(target):
+        """A stored Z with fl(Z - origin z) == target, searched in ulps around target + origin z; None if there is none."""
+        z0 = target + oz
+        for k in sorted(range(-16, 17), key=abs):
+            Z = z0
+            for _ in range(abs(k)):
+                Z = np.nextafter(Z, np.inf if k > 0 else -np.inf)
+            if Z - oz == target:
+                return Z
+        return None
+
+    edge_i, edge_j = (0, 7, 8, 15, 16, 19), (0, 3, 4, 11, 12, 19)      # image rows 19 | 16, 15 | 8, 7 | 0
+    free = [(i, j) for i in range(px) for j in range(px) if i not in edge_i and j not in edge_j]
+    reserved = [free[k] for k in rng.permutation(len(free))[:64]]
+    boundary, single, zeros = reserved[:44], reserved[44:58], reserved[58:64]
+    n_boundary = 0
+    for n, (i, j) in enumerate(boundary):
+        m = rng.integers(-1900, -1000) / 1000.
+        Zm = stored_z(m)
+        target = m + 0.2
+        Zs = [stored_z(target), stored_z(np.nextafter(target, np.inf)), stored_z(np.nextafter(target, -np.inf))]
+        if Zm is None or any(Z is None for Z in Zs):
+            continue                                               # (the cell stays empty)
+        n_boundary += 1
+        f_min, f_hi = (2, 0) if n % 2 else (0, 2)                  # both orders: the minimum after / before the rows it decides
+        add(f_min, i, j, Zm)
+        for Z, c8 in zip(Zs, (0., 2., 0.)):
+            add(f_hi, i, j, Z, c8=c8)
+        add(1, i, j, Zm + 0.7, c8=float(n % 3))                    # clearly elevated, whatever its column 8
+        add(1, i, j, Zm + 0.05, c8=float((n + 1) % 3))             # clearly not
+    for n, (i, j) in enumerate(single):
+        add(n % 3, i, j, rng.integers(-1500, 1000) / 1000. + oz)
+    for n, (i, j) in enumerate(zeros):                             # z0: the cell's minimum is a stored -0.0
+        add(0, i, j, -0.0)
+        add(2 if n % 2 else 0, i, j, 0.0 if n < 3 else 0.5)
+        add(1, i, j, 0.25, c8=2.)
+    for i in range(px):
+        for j in range(px):
+            if i in edge_i[1:5] or j in edge_j[1:5] or (i in (0, px - 1) and j in (0, px - 1)):   # both sides of every tile edge, the corners
+                add(int(rng.integers(0, 3)), i, j, rng.integers(-1500, 1400) / 1000. + oz, c8=float(rng.integers(0, 3)))
+    n_designed = sum(len(f) for f in frames)
+    taken = set(reserved)
+    while sum(len(f) for f in frames) < 1500:                      # the rest: random rows, also beyond the view and above the filter
+        i, j = int(rng.integers(-2, px + 2)), int(rng.integers(-2, px + 2))
+        if (i, j) in taken:
+            continue
+        add(int(rng.integers(0, 3)), i, j, rng.integers(-2000, 3000) / 1000. + oz, c8=float(rng.integers(0, 3)),
+            dyn=float(rng.random() < 0.15), jitter=0.45)
+    frames = [np.stack(f)[rng.permutation(len(f))] for f in frames]
+    k = 0
+    for f in frames:                                               # column 3: the row's index in the window
+        f[:, 3] = np.arange(k, k + f.shape[0])
+        k += f.shape[0]
+    n_rows = k
+    out = dict(frame0=frames[0], frame1=frames[1], frame2=frames[2], origin_a=origins['a'], origin_z0=origins['z0'],
+               cfg=np.array([view, px, hf, rot, dx, dy]))
+    grids = {}
+    for name, variant, use_hf, static_only, kt in ec.CASES:
+        gname = ec.grid_name(name)
+        if gname not in grids:
+            gen = ref.SemBEVGenerator(SEM_IDXS, view, px, 0., 0., False, 20., 20., 0.5, hf if use_hf else None)
+            rows = np.concatenate(frames)
+            rows[:, :3] = rows[:, :3] - origins[variant]           # kitti360_sem_pc_accum.py:193
+            grid, _ = gen.preprocess_pc_and_trajs(rows, [], rot, dx, dy, float(view))
+            if static_only:
+                _, grid = gen.partition_semantic_pc(grid, [1], 9)
+            assert (grid[:, 0:2] >= 0).all() and (grid[:, 0:2] < px).all()        # no cell index equal to px
+            assert not (np.signbit(grid[:, 2]) & (grid[:, 2] == 0)).any()         # no pre-gridded z of -0.0
+            grids[gname] = (gen, grid)
+            out[gname] = grid
+        gen, grid = grids[gname]
+        work = grid.copy()
+        pc_static, pc_dynamic, elevmap, mask = gen.static_obj_partitioning_by_elev(work, ec.THRESHOLDS[kt])
+        assert np.array_equal(pc_static, work[work[:, 8] == 0]) and np.array_equal(pc_dynamic, work[work[:, 8] == 1])
+        fate = np.full(n_rows, ec.FATE_OUT, dtype=np.int8)
+        fate[work[:, 3].astype(int)] = np.where(work[:, 8] == 0, ec.FATE_STATIC,
+                                                np.where(work[:, 8] == 1, ec.FATE_DYNAMIC, ec.FATE_NEITHER))
+        out[f'elev_{name}'], out[f'mask_{name}'], out[f'fate_{name}'] = elevmap, mask, fate
+    # what the reference delivers for a stored -0.0 under origin z 0: +0.0 in the map
+    emap, mask = out['elev_z0_hf0_dyn1_t0'], out['mask_z0_hf0_dyn1_t0']
+    for i, j in zeros:
+        assert mask[px - 1 - j, i] and emap[px - 1 - j, i] == 0. and not np.signbit(emap[px - 1 - j, i]), (i, j)
+    assert n_boundary >= 30, n_boundary
+    path = os.path.join(out_dir, 'elev_partition.npz')
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 400 * 1024, os.path.getsize(path)
+    print('elev_partition:', [f.shape[0] for f in frames], 'rows,', n_designed, 'designed,', n_boundary, 'boundary cells,',
+          len(single), 'single-row cells,', os.path.getsize(path), 'bytes')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(
@@ -1205,7 +1321,7 @@ def main():
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
                  bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
                  utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes,
-                 sweeps_edges=case_sweeps_edges)
+                 sweeps_edges=case_sweeps_edges, elev_partition=case_elev_partition)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
