@@ -495,15 +495,23 @@ int pca_bev_view_hint(pca_ctx *ctx, int slot0, int F, const double *then, const 
                       const pca_bev_params *prm);
 void pca_f32_box_decode(const uint32_t *rows /*[n][6]*/, int n, float *box /*[n][6]: lo x, hi x, lo y, ...; lo > hi = empty*/);
 
+/* Diagnostics (read only; nothing here changes what a call computes).
+ * pca_debug_bev_level1: level 1's grid as the context's last pca_bev_generate_chain (pca_kitti_generate_bev included) launched
+ *     it: out = {G workgroups, Gk of them tiles of a riding K1, bin_first, bin_end: the slots level 1 read from the store --
+ *     the window, or what pca_bev_bin_range / pca_bev_view_hint left of it}.  G == the device's compute units with a bin range
+ *     set: a one-round launch.  0 / -1. */
+int pca_debug_bev_level1(const pca_ctx *ctx, int out[4]);
+
 /* K1 of pca_kitti_integrate left for the raster that follows it.  The reference's driver integrates a frame and, when its
  * trigger fires, rasterises the window that ends with that frame (run_kitti360_bev_gen.py:186-273): with on = 1, a
- * pca_kitti_integrate whose inputs are the plain kind (nearest sampling, rgb + class map) does the pose bookkeeping and the
+ * pca_kitti_integrate whose inputs are the plain kind (nearest sampling; rgb + class map, or per-point labels) does the pose bookkeeping and the
  * staging as before but only NOTES its K1; the next pca_bev_generate_chain / pca_kitti_generate_bev of the context whose
  * window ends with that slot (same store, frame_off and stream, 5 planes x int32 layout) runs it as the first workgroups
  * of its own first kernel -- the frame's kept points go into the store AND, straight from registers, into the raster's
  * tile lists, so they are not read back.  Every other entry point that reads or writes a store runs a noted K1 first, on
  * its own (the order of effects on `stream` is the order of the calls, as without deferral); so does pca_status.  Until
- * then the DEVICE pointers of the observation must stay valid (host arrays are held in the context's staging block).
+ * then -- the next library call on the context -- the DEVICE buffers of the observation must stay UNMODIFIED, not only
+ * allocated: the noted K1 reads them when it runs (host arrays are held in the context's staging block).
  * pca_k1_defer(ctx, 0) turns it off and runs what is noted; pca_k1_flush runs what is noted.  0 / -1. */
 int pca_k1_defer(pca_ctx *ctx, int on);
 int pca_k1_flush(pca_ctx *ctx);

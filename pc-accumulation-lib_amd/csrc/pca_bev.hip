@@ -2057,6 +2057,7 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
     if (bev_decide_k1_ride(ctx, a, tuned, lds, s, &k1a, &nt)) return -1;
     const int one_round = bev_decide_bin_range(ctx, a, tuned, bin_range);
     bev_size_level1(ctx, a, nt, one_round);
+    ctx->last_level1[0] = a.G; ctx->last_level1[1] = a.Gk; ctx->last_level1[2] = a.bin_first; ctx->last_level1[3] = a.bin_end;
     // A banded raster: every band is one level-1 pass over the window and the tile kernels over the band's tiles, in the caller's
     // planes; all bands share the workspace, one after the other on `s`.  Owed transforms: with write_back, band 0 applies and
     // stores them and the later bands read the updated store (n_pend = 0); without, every band applies them on the fly.  Every
@@ -2211,6 +2212,14 @@ int pca_bev_warp(pca_ctx *ctx, const uint16_t *planes_f16, uint16_t *out_f16, in
 int pca_debug_bev_stamps(unsigned long long *out)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg_stamps), sizeof(unsigned long long) * 8192);
+}
+
+// diagnostic, read only: level 1's grid as the last pca_bev_generate_chain of the context launched it
+int pca_debug_bev_level1(const pca_ctx *ctx, int out[4])
+{
+    if (!ctx || !out) return -1;
+    for (int k = 0; k < 4; ++k) out[k] = ctx->last_level1[k];
+    return 0;
 }
 
 }  // extern "C"

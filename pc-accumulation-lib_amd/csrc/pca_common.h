@@ -108,6 +108,7 @@ struct pca_ctx {
     uint32_t *heavy_hint_dev = nullptr;
     int bin_first = 0, bin_end = 0;   // pca_bev_bin_range: the slots the next single raster bins (bin_valid); forgotten by that call
     bool bin_valid = false;
+    int last_level1[4] = {0, 0, 0, 0};   // diagnostics (pca_debug_bev_level1): G, Gk, bin_first, bin_end of the last pca_bev_generate_chain
     // optional per-kernel event timing
     struct Ev { hipEvent_t a, b; int kid; };
     int profiling = 0;                // 0 off, 1 every kernel launch, 2 whole units only (pca_profile_enable)
