@@ -59,6 +59,7 @@ typedef struct {
 #define PCA_STATUS_UV_OUT_OF_IMAGE 2u /* NuScenes: pixel coords outside (1, wh-1): reference AssertionError */
 #define PCA_STATUS_NEGATIVE_INTENSITY 4u /* BEV: a negative f32 intensity (pass intensity64 for such data)   */
 #define PCA_STATUS_LOOKBACK_TIMEOUT 8u /* a compaction workgroup gave up waiting for a predecessor (output invalid) */
+#define PCA_STATUS_LANES_BISECT_CAP 16u /* lanes: a border crossing was not found within 1100 halvings (row invalid) */
 
 int pca_version(void);
 int pca_ctx_create(int device, pca_ctx **out);
@@ -437,12 +438,45 @@ int pca_bev_warp(pca_ctx *ctx, const uint16_t *planes_f16 /*dev*/, uint16_t *out
 /* ------------------------------------------------------------------------------------------------
  * Host helper (no device work): the ego trajectory of one BEV sample -- rotate, translate, clip to the view box
  * with bisected border crossings, grid coordinates.  Replaces bev_generator/bev_generator.py:207-371, :737-747 for
- * the ego polyline (plain IEEE arithmetic, bit-identical to the numpy form in pca_amd/host_logic.py).
+ * the ego polyline (plain IEEE arithmetic, bit-identical to the numpy form in pca_amd/host_logic.py; the rotation's sums
+ * begin from +0.0 as numpy's do, which decides the sign of a zero z).
  * full: host [F,3] f64; R: 3x3 row-major; rows: host [2(F-1),3] out; start: host [F] out (first row of every
  * edge; start[F-1] = number of rows).  Returns the number of rows.
  * ------------------------------------------------------------------------------------------------ */
 int pca_host_ego_to_grid(const double *full, int F, const double R[9], double dx, double dy, double view, int px,
                          double *rows, int32_t *start);
+
+/* ------------------------------------------------------------------------------------------------
+ * KL  the ground-truth lane centrelines of a whole map, clipped to the BEV of S samples in one launch set.
+ *     Replaces bev_generator/bev_generator.py:101-109 (preprocess_pc_and_trajs on a dummy cloud with every lane, then the
+ *     non-empty filter) with geometric_transform(is_traj=True) :207-237, crop_trajectory / cal_intersec_pnt :257-371 and
+ *     pos2grid :737-747 underneath, as nuscenes_oracle_sem_pc_accum.py:173-176, :552-554 feed it (lane - bev_frame_coords),
+ *     and the once-per-scene homo_transform per lane of nuscenes_oracle_sem_pc_accum.py:71, :171.
+ *     The lane set: xyz dev [P,3] f64, the vertices of the L lanes one after the other; start dev [L+1] i32, lane i owns
+ *     vertices start[i] .. start[i+1]-1; vertex_lane dev [P] i32, the lane of every vertex (an edge joins two consecutive
+ *     vertices of the same lane; the present kernels read the lane boundaries from vertex_lane alone).
+ * pca_lanes_transform  xyz <- (T [p; 1])[:3] in place (T: host, 4x4 row-major): the f64 fma chain in k order of K1n / K2,
+ *     bit-equal to datasets.nuscenes_utils.homo_transform lane by lane.
+ * pca_lanes_to_grid    per sample k and edge a -> b, with the roundings of pca_host_ego_to_grid on (lane - views[k].origin):
+ *     an inside `a` gives a row, an edge with exactly one end inside additionally the bisected crossing carrying a's z; x, y
+ *     are floor(v / view * px + 0.5 px).  rows: dev [S][cap_rows][3] f64 in edge order (= map order); row_lane: dev
+ *     [S][cap_rows] the row's lane; n_rows: dev [S] the TRUE count -- rows beyond cap_rows are not written: run that sample
+ *     again with cap_rows >= n_rows.  ws: dev, pca_lanes_workspace_bytes(P, S, cap_rows) bytes.  Three launches and a fetch of
+ *     the views, no synchronisation; P < 2, L == 0: n_rows is zeroed, nothing is launched; S == 0: nothing is done.  A
+ *     crossing not found within 1100 halvings raises PCA_STATUS_LANES_BISECT_CAP (no finite input gets there).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    double origin[3];          /* bev_frame_coords: subtracted from every vertex first */
+    double R[9];               /* rotation, row-major */
+    double dx, dy, view;       /* shift [m], aug_view_size [m] */
+    int32_t px, reserved;      /* pixel_size */
+} pca_lane_view;
+int64_t pca_lanes_workspace_bytes(int64_t n_vertices, int n_samples, int64_t cap_rows);
+int pca_lanes_transform(pca_ctx *ctx, double *xyz /*dev*/, int64_t P, const double T[16], void *stream);
+int pca_lanes_to_grid(pca_ctx *ctx, const double *xyz /*dev*/, const int32_t *vertex_lane /*dev*/, const int32_t *start /*dev*/,
+                      int64_t P, int32_t L, const pca_lane_view *views /*host [S]*/, int S, int64_t cap_rows,
+                      double *rows /*dev [S][cap][3]*/, int32_t *row_lane /*dev [S][cap]*/, int64_t *n_rows /*dev [S]*/, void *ws,
+                      void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * One library call per driver call (KITTI-360 flow).  The reference's driver calls integrate(observations) per frame and

@@ -89,11 +89,13 @@ class BEVGenerator(ABC):
         self._device_only = False
         self._out16 = None
         self._defer = None                  # a list while rasters are being collected for ONE launch (raster_batch)
+        self._lane_defer = None             # likewise the samples' lane views (one pca_lanes_to_grid for all of them)
 
     def __getstate__(self):                 # device handles never travel through pickle
         d = dict(self.__dict__)
         d['_tmp'] = {}
         d['_defer'] = None
+        d['_lane_defer'] = None
         return d
 
     class _RasterBatch:
@@ -106,6 +108,13 @@ class BEVGenerator(ABC):
 
         def __exit__(self, exc_type, exc, tb):
             jobs, self.gen._defer = self.gen._defer, None
+            if self.gen._lane_defer is not None:   # the lanes of all the samples: ONE call, one copy to the host
+                lane_jobs, self.gen._lane_defer = self.gen._lane_defer, None
+                if exc_type is not None:
+                    return False
+                lanes = lane_jobs[0][0]
+                assert all(j[0] is lanes for j in lane_jobs)
+                lanes.to_grid([j[1] for j in lane_jobs], asynchronous=True, into=[j[2] for j in lane_jobs])
             if exc_type is None and jobs:
                 store = jobs[0][0]
                 assert all(j[0] is store for j in jobs)
@@ -223,7 +232,22 @@ class BEVGenerator(ABC):
             trajs_full = [ego_a] + to_grid(oth_full)
         else:
             trajs_present = to_grid([ego_present] + oth_present)
-        if lanes is not None:
+        if lanes is not None and not isinstance(lanes, list):
+            # a device lane set (pca_amd.lanes.LaneHandle): clipped there, for this sample alone or -- inside raster_batch --
+            # with the other samples of the batch; what comes back is pending until somebody looks at it
+            from pca_amd.lanes import LaneView, PendingLanes
+            view = LaneView(lanes.origin, rot_mat, trans_dx, trans_dy, aug_view_size, self.pixel_size)
+            if self._defer is not None and device_only:
+                if self._lane_defer is None:
+                    self._lane_defer = []
+                pending = PendingLanes()
+                self._lane_defer.append((lanes.lanes, view, pending))
+                lanes = pending
+            else:
+                lanes = lanes.lanes.to_grid([view], asynchronous=device_only)[0]
+                if not device_only:
+                    lanes = lanes.resolve()
+        elif lanes is not None:
             lanes = [lane for lane in to_grid(lanes) if lane.shape[0] > 0]
         if pc_future is None:
             # the reference only defines the future/full trajectories inside `if pc_future is not None`

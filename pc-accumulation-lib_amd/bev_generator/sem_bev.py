@@ -74,6 +74,8 @@ class LazyBev(dict):
             planes = host[index].numpy()
             if not self._zero_copy:
                 planes = np.array(planes)
+            if gt_lanes is not None and not isinstance(gt_lanes, list):     # pca_amd.lanes.PendingLanes: decoded now
+                gt_lanes = gt_lanes.resolve()
             dict.update(self, SemBEVGenerator.pack_bev(planes, trajs[0], trajs[1], trajs[2], gt_lanes))
             self._pending = None                 # only now: the sample is complete
         return self
@@ -174,8 +176,10 @@ class SemBEVGenerator(BEVGenerator):
             trajs_present = self.warp_trajs(trajs_present, *args)
             trajs_future = self.warp_trajs(trajs_future, *args)
             trajs_full = self.warp_trajs(trajs_full, *args)
-            if gt_lane_trajs is not None:
+            if isinstance(gt_lane_trajs, list):
                 gt_lane_trajs = self.warp_trajs(gt_lane_trajs, *args)
+            elif gt_lane_trajs is not None:          # pending device lanes: warped when they are decoded (few are left)
+                gt_lane_trajs.then(lambda lanes, args=args: self.warp_trajs(lanes, *args))
         if device_only:
             out = {'planes_f16': p16, 'trajs_present': trajs_present, 'trajs_future': trajs_future,
                    'trajs_full': trajs_full}

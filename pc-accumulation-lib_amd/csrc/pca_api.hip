@@ -221,9 +221,12 @@ int pca_host_ego_to_grid(const double *full, int F, const double R[9], double dx
     if (F < 2) { if (F == 1 && start) start[0] = 0; return 0; }
     const double h = 0.5 * view, lo = -h, pxd = (double)px, half_px = 0.5 * pxd;
     auto rot = [&](const double *p, double &x, double &y, double &z) {
-        x = fma(R[2], p[2], fma(R[1], p[1], R[0] * p[0])) + dx;
-        y = fma(R[5], p[2], fma(R[4], p[1], R[3] * p[0])) + dy;
-        z = fma(R[8], p[2], fma(R[7], p[1], R[6] * p[0]));
+        // (numpy adds the products onto +0.0: where every product is a -0.0 -- a z of -0.0 left and below the origin -- the
+        // result is +0.0, not the -0.0 a sum begun from the first product would give.  product + 0.0 is fma(a, b, 0.0)
+        // without a third call into libm per row: this runs for every pose of every sample)
+        x = fma(R[2], p[2], fma(R[1], p[1], R[0] * p[0] + 0.0)) + dx;
+        y = fma(R[5], p[2], fma(R[4], p[1], R[3] * p[0] + 0.0)) + dy;
+        z = fma(R[8], p[2], fma(R[7], p[1], R[6] * p[0] + 0.0));
     };
     auto emit = [&](int m, double x, double y, double z) {
         rows[3 * m + 0] = floor(x / view * pxd + half_px);

@@ -44,9 +44,47 @@ class NuScenesOracleSemanticPointCloudAccumulator(SemanticPointCloudAccumulator)
         self.ego_global_xs = []
         self.ego_global_ys = []
         self.get_gt_lanes = get_gt_lanes
+        self._lanes = None              # the lane set: a pca_amd.lanes.DeviceLanes, or the reference's list (PCA_GT_LANES=host)
         if self.get_gt_lanes:
             from datasets.nuscenes_lanemap import get_centerlines
-            self.gt_lane_poses = get_centerlines(dataroot, loc)
+            self.set_gt_lanes(get_centerlines(dataroot, loc))
+
+    # ---- GT lane centrelines ---------------------------------------------------------------------
+    def set_gt_lanes(self, lanes):
+        """The map's lane centrelines, a list of (k,3) arrays in 'global' coordinates (what get_centerlines returns; a caller
+        without the devkit hands its own list in).  Call before the first integrate(): that is where they move to the 'world'
+        frame.  They live on the device (pca_amd.lanes.DeviceLanes) and every sample clips them there in one launch set;
+        PCA_GT_LANES=host keeps the reference's host lists and its per-lane loops."""
+        self._keep_lanes(lanes)
+        if self.T_global_world is not None:          # the scene has begun: the lanes follow it into the 'world' frame now
+            self._lanes_to_world()
+
+    def _keep_lanes(self, lanes):
+        import os
+        self.get_gt_lanes = True
+        if os.environ.get('PCA_GT_LANES', 'device') == 'host':
+            self._lanes = [np.asarray(lane, dtype=np.float64) for lane in lanes]
+        else:
+            from pca_amd.lanes import DeviceLanes
+            self._lanes = DeviceLanes(lanes, self.store.device)
+
+    @property
+    def gt_lane_poses(self):
+        """The reference's attribute: the list of (k,3) arrays (materialised from the device on every read)."""
+        if self._lanes is None:
+            raise AttributeError('gt_lane_poses')
+        return self._lanes if isinstance(self._lanes, list) else self._lanes.as_list()
+
+    @gt_lane_poses.setter
+    def gt_lane_poses(self, lanes):             # (as the reference assigns it: the list as it is, in whatever frame)
+        self._keep_lanes(lanes)
+
+    def _lanes_to_world(self):
+        """nuscenes_oracle_sem_pc_accum.py:71, :171 of the reference: homo_transform per lane, once per scene."""
+        if isinstance(self._lanes, list):
+            self._lanes = [homo_transform(self.T_global_world, lane) for lane in self._lanes]
+        elif self._lanes is not None:
+            self._lanes.transform(self.T_global_world)
 
     # tracker state under the reference's attribute names
     @property
@@ -68,7 +106,7 @@ class NuScenesOracleSemanticPointCloudAccumulator(SemanticPointCloudAccumulator)
         if self.T_global_world is None:
             self.T_global_world = np.linalg.inv(T_ego_global)
             if self.get_gt_lanes:
-                self.gt_lane_poses = [homo_transform(self.T_global_world, lane) for lane in self.gt_lane_poses]
+                self._lanes_to_world()
 
         pose, semsegs = self._append_frame(obs['images'], obs['pc'], obs['pc_cam_idx'], T_ego_global,
                                            self.ego_pose_z)
@@ -168,7 +206,7 @@ class NuScenesOracleSemanticPointCloudAccumulator(SemanticPointCloudAccumulator)
             if self.T_global_world is None:
                 self.T_global_world = np.linalg.inv(T_ego_global)
                 if self.get_gt_lanes:
-                    self.gt_lane_poses = [homo_transform(self.T_global_world, lane) for lane in self.gt_lane_poses]
+                    self._lanes_to_world()
             T_ego_world, pose = self._ego_world(T_ego_global, self.ego_pose_z)
             pc_d, cam_d, imgs, sems, semsegs = self._frame_inputs(obs['images'], obs['pc'], obs['pc_cam_idx'])
             frames.append(dict(pc=pc_d, cam_idx=cam_d, imgs=imgs, sems=sems, T=T_ego_world))
@@ -212,7 +250,7 @@ class NuScenesOracleSemanticPointCloudAccumulator(SemanticPointCloudAccumulator)
     # ---- BEV -----------------------------------------------------------------------------------
     def _window_inputs_for(self, present_idx, gen_future):
         others = self.get_split_dyn_obj_trajs(present_idx)
-        lanes = self.gt_lane_poses if self.get_gt_lanes else None
+        lanes = self._lanes if self.get_gt_lanes else None
         return self._window_inputs(present_idx, gen_future, others, lanes)
 
     def generate_bev(self, present_idx: int = None, bev_num: int = 1, gen_future: bool = False):

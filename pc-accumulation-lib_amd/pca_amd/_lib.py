@@ -15,6 +15,7 @@ STATUS_STORE_OVERFLOW = 1
 STATUS_UV_OUT_OF_IMAGE = 2
 STATUS_NEGATIVE_INTENSITY = 4
 STATUS_LOOKBACK_TIMEOUT = 8
+STATUS_LANES_BISECT_CAP = 16
 SAMPLE_MODES = {'nearest': 0, 'bilinear': 1}
 
 EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error', 'pca_status', 'pca_status_peek', 'pca_status_mirror',
@@ -22,7 +23,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
            'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
-           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_warp', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
+           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
            'pca_host_track_poses', 'pca_host_track_segments', 'pca_host_track_set', 'pca_host_track_transform',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
@@ -201,6 +202,11 @@ def load():
                                      C.c_double, vp, i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int), vp]
     lib.pca_host_ego_to_grid.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]
+    lib.pca_lanes_workspace_bytes.argtypes = [i64, i32, i64]
+    lib.pca_lanes_workspace_bytes.restype = i64
+    lib.pca_lanes_transform.argtypes = [vp, vp, i64, vp, vp]
+    # (views: a ctypes array of pca_amd.lanes.PcaLaneView, or its address)
+    lib.pca_lanes_to_grid.argtypes = [vp, vp, vp, vp, i64, C.c_int32, vp, i32, i64, vp, vp, vp, vp, vp]
     dp = C.POINTER(C.c_double)
     lib.pca_host_gemv4_probe.argtypes = [vp, i32, vp, vp, i64, vp]
     lib.pca_host_gemv4_mode.argtypes = [i32]
@@ -349,9 +355,10 @@ class Context:
                 (STATUS_STORE_OVERFLOW, RuntimeError, 'pca: device point store overflow (points were dropped)'),
                 (STATUS_LOOKBACK_TIMEOUT, RuntimeError,
                  'pca: a compaction workgroup timed out waiting for its predecessor (output invalid)'),
-                (STATUS_NEGATIVE_INTENSITY, ValueError, 'pca: negative lidar intensity on the f32 path (pass intensity64 to bev())')]
+                (STATUS_NEGATIVE_INTENSITY, ValueError, 'pca: negative lidar intensity on the f32 path (pass intensity64 to bev())'),
+                (STATUS_LANES_BISECT_CAP, RuntimeError, 'pca: a lane\'s border crossing was not found within the iteration cap (row invalid)')]
         hit = [(exc, msg) for bit, exc, msg in said if st & bit]
-        rest = st & ~(STATUS_UV_OUT_OF_IMAGE | STATUS_STORE_OVERFLOW | STATUS_LOOKBACK_TIMEOUT | STATUS_NEGATIVE_INTENSITY)
+        rest = st & ~(STATUS_UV_OUT_OF_IMAGE | STATUS_STORE_OVERFLOW | STATUS_LOOKBACK_TIMEOUT | STATUS_NEGATIVE_INTENSITY | STATUS_LANES_BISECT_CAP)
         if rest:
             hit.append((RuntimeError, 'pca: unknown device status bits 0x%x' % rest))
         raise hit[0][0]('; '.join(msg for _, msg in hit))

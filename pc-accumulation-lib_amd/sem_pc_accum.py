@@ -275,7 +275,11 @@ class SemanticPointCloudAccumulator:
         others = other_trajs if other_trajs is not None else ([], [], [])
         trajs['other_trajs_present'] = [np.concatenate([t]) - origin for t in others[0]]
         if gt_lanes is not None:
-            trajs['gt_lanes'] = [lane - origin for lane in gt_lanes]
+            if isinstance(gt_lanes, list):
+                trajs['gt_lanes'] = [lane - origin for lane in gt_lanes]
+            else:                                    # a device lane set: a handle, not L shifted copies
+                from pca_amd.lanes import LaneHandle
+                trajs['gt_lanes'] = LaneHandle(gt_lanes, origin)
         if gen_future:
             if split >= self.store.n_frames and not all_sets:
                 raise ValueError('need at least one array to concatenate')
@@ -366,6 +370,10 @@ class SemanticPointCloudAccumulator:
     @staticmethod
     def _copy_trajs(trajs):
         out = {}
+        lanes = trajs.get('gt_lanes')
+        if lanes is not None and not isinstance(lanes, list):       # a pca_amd.lanes.LaneHandle passes through as it is
+            trajs = dict(trajs)
+            out['gt_lanes'] = trajs.pop('gt_lanes')
         for k, v in trajs.items():
             if isinstance(v, list):
                 out[k] = [np.array(t) for t in v]

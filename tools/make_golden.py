@@ -1308,6 +1308,170 @@ def case_elev_partition(ref, out_dir):
           len(single), 'single-row cells,', os.path.getsize(path), 'bytes')
 
 
+def lanes_map_and_views():
+    """The hand-built lane map and views of tests/golden/lanes.npz (design coordinates are those of the 'world' frame; the
+    map is handed to the reference in 'global' coordinates, T_global_world brings it back -- up to rounding, which is why
+    the views that need a vertex exactly on their border are sized from the transformed vertex itself, in case_lanes)."""
+    rng = np.random.default_rng(101)
+    c, s_ = np.cos(0.3), np.sin(0.3)
+    # planar, as the inverse of an ego pose with yaw only
+    T = np.array([[c, -s_, 0., 300.], [s_, c, 0., 200.], [0., 0., 1., 0.5], [0., 0., 0., 1.]])
+    views = [  # origin, rot, dx, dy, zoom, px, view_size
+        ((0., 0., 0.), 0., 0., 0., 1., 64, 40.),
+        ((3.5, -2.25, 0.5), 0.7, 1.5, -0.75, 1.07, 256, 40.),
+        ((-6., 4., 1.), 0.5 * np.pi, -2., 0.5, 0.9, 7, 40.),
+        ((1., 1., 0.), -2.1, 0.3, 0.4, 1., 64, 40.),
+        ((0., 0., 0.), 0., 0., 0., 1.07, 256, 40.),
+        ((10., -12., 0.3), 0.7, 0., 0., 0.9, 7, 40.),
+        ((500., 500., 0.), 0.7, 0., 0., 1., 64, 40.),          # no lane survives
+        ((0., 0., 0.), 0.7, 0., 0., 1., 256, 400.),            # every finite vertex is inside
+        ((-3., 7., 0.), 0.5 * np.pi, 2.5, -1.5, 1.07, 64, 40.),
+        ((5., 5., 0.5), -2.1, 0., 0., 0.9, 256, 40.),
+        ((-2., 3., 0.), 0., 4.25, -3.5, 0.9, 7, 40.),
+        ((0., 0., 0.), 0.7, 0., 0., 1., 64, 40.),
+    ]
+
+    def rot2(ang):
+        return np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
+
+    def to_world(v, pts):
+        """Design points given in the (metric) frame of view v -> world."""
+        origin, rot, dx, dy = v[0], v[1], v[2], v[3]
+        pts = np.array(pts, dtype=np.float64)
+        out = pts.copy()
+        out[:, :2] = (pts[:, :2] - [dx, dy]) @ rot2(rot) + origin[:2]      # inverse of the rotation: R^T p as rows p R
+        out[:, 2] = pts[:, 2] + origin[2]
+        return out
+
+    lanes, names = [], {}
+
+    def add(name, pts):
+        names[name] = len(lanes)
+        lanes.append(np.array(pts, dtype=np.float64).reshape(-1, 3))
+
+    add('len0', np.zeros((0, 3)))
+    add('len1', [[1., 2., 0.1]])
+    add('len2', [[-3., 2., 0.2], [-2., 3., 0.3]])
+    add('len3', [[4., -5., 0.1], [5., -6., 0.], [6., -5.5, -0.1]])
+    add('inside', np.c_[np.linspace(-8, 8, 10), 3 * np.sin(np.linspace(0, 3, 10)), np.linspace(0, 1, 10)])
+    add('outside', np.c_[np.linspace(42, 55, 10), np.linspace(44, 47, 10), np.zeros(10)])
+    add('zigzag', np.c_[np.linspace(-12, 12, 12), np.where(np.arange(12) % 2, 26., 15.), np.linspace(-0.3, 0.3, 12)])
+    add('through', [[-35., 3., 0.1], [35., 4., 0.2], [36., 30., 0.3]])
+    add('long_in_out', [[2., 1., 0.4], [70., 33., 0.5]])
+    add('long_out_in', [[-80., -5., 0.6], [1., -2., 0.7], [2., -3., 0.8]])
+    add('tiny_x', [[19.5, 5., 0.1], [19.99999, 5., 0.2], [20.00001, 5.000001, 0.3], [20.5, 5., 0.4]])
+    add('tiny_y', [[-7., -19.5, 0.1], [-7., -19.999992, 0.2], [-7.000001, -20.000009, 0.3], [-7., -19.5, 0.4]])
+    add('nan_mid', [[6., 6., 0.1], [7., 7., 0.2], [8., 8., 0.3], [9., 7., 0.4], [10., 6., 0.5]])
+    add('inf_mid', [[-6., 6., 0.1], [-7., 7., 0.2], [-8., 8., 0.3], [-9., 7., 0.4], [-10., 6., 0.5]])
+    add('border_xp', [[1., 2., 0.1], [13.3, 3., 0.2], [2., 1., 0.3]])
+    add('border_xm', [[-1., 2., 0.1], [-11.7, -3., 0.2], [-2., 1., 0.3]])
+    add('border_yp', [[1., 2., 0.1], [3., 12.1, 0.2], [2., 1., 0.3]])
+    add('border_ym', [[1., -2., 0.1], [-3., -14.9, 0.2], [2., -1., 0.3]])
+    v1 = views[1]
+    h1 = 0.5 * v1[4] * v1[6]
+    lanes.append(to_world(v1, [[h1 - 0.5, 2., 0.1], [h1 - 0.00001, 2., 0.2], [h1 + 0.00001, 2., 0.3], [h1 + 1., 2., 0.4]]))
+    names['tiny_v1'] = len(lanes) - 1
+    lanes.append(to_world(v1, [[-3., -4., 0.1], [1.6 * 42.8, 11., 0.2], [-60., -70., 0.3], [0., 1., 0.4]]))
+    names['long_v1'] = len(lanes) - 1
+    for k in range(120):
+        n = int(rng.integers(2, 13))
+        start = np.r_[rng.uniform(-35, 35, 2), rng.uniform(-0.5, 0.5)]
+        steps = np.c_[rng.normal(0, 3, (n, 2)), rng.normal(0, 0.05, n)]
+        steps[0] = 0
+        lanes.append(start + np.cumsum(steps, axis=0))
+    world_design = lanes
+    Ti = np.linalg.inv(T)
+    glob = []
+    for lane in world_design:
+        glob.append(lane @ Ti[:3, :3].T + Ti[:3, 3])
+    glob[names['nan_mid']][2, 0] = np.nan
+    glob[names['inf_mid']][2, 0] = np.inf
+    return T, glob, views, names
+
+
+def case_lanes(ref, out_dir):
+    """GT lane centrelines through the reference itself: homo_transform per lane (nuscenes_oracle_sem_pc_accum.py:173-176),
+    lane - bev_frame_coords (:552-554), then BEVGenerator.preprocess_pc_and_trajs on a dummy cloud with every lane and the
+    non-empty filter (bev_generator.py:101-109), for every view: tests/golden/lanes.npz.  Data only: the map ('global' and
+    'world' vertices, packed, with the lanes' first vertices), T, the views and per view the surviving lanes' rows, packed,
+    with their lengths."""
+    T, glob, views, names = lanes_map_and_views()
+    world = [ref.nu.homo_transform(T, lane) for lane in glob]
+    # A stored z of -0.0 cannot come out of homo_transform (numpy's product adds onto +0.0), so the lanes that hold one are
+    # a second, tiny set in 'world' coordinates that goes through the same subtraction and preprocess_pc_and_trajs:
+    # p - origin in the (+, +) quadrant, where the rotation's 0 x + 0 y is +0.0, and in the (-, -) quadrant, where every
+    # product is a -0.0: the z comes out +0.0 in both (numpy adds the products onto +0.0)
+    nz = [np.array([[3., 4., -0.0], [4., 5., 0.25], [30., 5., -0.0]]), np.array([[-3., -4., -0.0], [-4., -5., -0.0], [-30., -5., 0.25]])]
+    # views with a vertex exactly on +-view/2 (outside), and with the border one ulp beyond it (inside): origin 0, no
+    # rotation, no shift, zoom 1, sized from the transformed vertex
+    n_general = len(views)
+    for name, axis in (('border_xp', 0), ('border_xm', 0), ('border_yp', 1), ('border_ym', 1)):
+        cval = abs(world[names[name]][1, axis])
+        views.append(((0., 0., 0.), 0., 0., 0., 1., 64, 2. * cval))
+        views.append(((0., 0., 0.), 0., 0., 0., 1., 64, 2. * np.nextafter(cval, np.inf)))
+    start = np.zeros(len(glob) + 1, dtype=np.int32)
+    np.cumsum([g.shape[0] for g in glob], out=start[1:])
+    out = dict(T=T, start=start, xyz_global=np.concatenate(glob), xyz_world=np.concatenate(world),
+               names=np.array(sorted(names, key=names.get)), name_lane=np.array(sorted(names.values()), dtype=np.int32))
+    table, Rs = [], []
+    survivors = []
+    for k, (origin, rot, dx, dy, zoom, px, view_size) in enumerate(views):
+        gen = ref.SemBEVGenerator(SEM_IDXS, view_size, px, 0., 0., False, 20., 20., 0.5, None)
+        origin = np.array(origin)
+        lanes_k = [lane - origin for lane in world]                                    # :552-554
+        # which lanes survive: the reference drops the empty ones; their indices come from a marker run on copies
+        dummy = np.zeros((1, 10))
+        with np.errstate(invalid='ignore'):
+            _, res = gen.preprocess_pc_and_trajs(dummy, [lane.copy() for lane in lanes_k], rot, dx, dy, zoom * view_size)
+        kept = [i for i, lane in enumerate(res) if lane.shape[0] > 0]
+        res = [lane for lane in res if lane.shape[0] > 0]                              # bev_generator.py:107-109
+        out[f'rows_{k}'] = np.concatenate(res) if res else np.zeros((0, 3))
+        out[f'len_{k}'] = np.array([lane.shape[0] for lane in res], dtype=np.int32)
+        out[f'kept_{k}'] = np.array(kept, dtype=np.int32)
+        table.append([origin[0], origin[1], origin[2], rot, dx, dy, zoom, px, view_size])
+        Rs.append(gen.rotation_matrix_3d(rot))
+        survivors.append(kept)
+    out['views'], out['R'] = np.array(table), np.stack(Rs)
+    # the cases the map was built for, checked on what the reference returned
+    def rows_of(k, name):
+        i = names[name]
+        if i not in survivors[k]:
+            return np.zeros((0, 3))
+        j = survivors[k].index(i)
+        o = int(out[f'len_{k}'][:j].sum())
+        return out[f'rows_{k}'][o:o + out[f'len_{k}'][j]]
+    assert len(survivors[6]) == 0 and len(survivors[7]) == sum(g.shape[0] >= 2 for g in glob)
+    assert rows_of(0, 'inside').shape[0] == 9 and rows_of(0, 'outside').shape[0] == 0
+    assert rows_of(0, 'through').shape[0] == 0                     # both ends outside: nothing, although it passes through
+    assert rows_of(0, 'zigzag').shape[0] >= 3 * 3                  # in and out again and again
+    assert rows_of(0, 'long_in_out').shape[0] == 2 and rows_of(0, 'long_out_in').shape[0] == 2
+    assert rows_of(0, 'tiny_x').shape[0] == 3 and rows_of(0, 'tiny_y').shape[0] == 4
+    assert rows_of(1, 'tiny_v1').shape[0] == 3 and rows_of(1, 'long_v1').shape[0] == 3
+    out['nz_xyz'], out['nz_start'] = np.concatenate(nz), np.array([0, 3, 6], dtype=np.int32)
+    for k in (0, 3):
+        origin, rot, dx, dy, zoom, px, view_size = views[k]
+        gen = ref.SemBEVGenerator(SEM_IDXS, view_size, px, 0., 0., False, 20., 20., 0.5, None)
+        _, res = gen.preprocess_pc_and_trajs(np.zeros((1, 10)), [lane - np.array(origin) for lane in nz], rot, dx, dy,
+                                             zoom * view_size)
+        assert all(lane.shape[0] > 0 for lane in res)
+        out[f'nz_rows_{k}'] = np.concatenate(res)
+        out[f'nz_len_{k}'] = np.array([lane.shape[0] for lane in res], dtype=np.int32)
+    z = out['nz_rows_0'][0, 2]
+    assert z == 0 and not np.signbit(z)
+    z = out['nz_rows_0'][out['nz_len_0'][0], 2]
+    assert z == 0 and not np.signbit(z)
+    assert rows_of(0, 'nan_mid').shape[0] == 5 and np.isnan(rows_of(0, 'nan_mid')[2, 0])
+    assert rows_of(0, 'inf_mid').shape[0] == 5 and not np.isfinite(rows_of(0, 'inf_mid')[2, :2]).all()
+    for j, name in enumerate(('border_xp', 'border_xm', 'border_yp', 'border_ym')):
+        assert rows_of(n_general + 2 * j, name).shape[0] == 3, name        # on the border: outside, two crossings
+        assert rows_of(n_general + 2 * j + 1, name).shape[0] == 2, name    # one ulp inside: no crossing
+    path = os.path.join(out_dir, 'lanes.npz')
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 256 * 1024, os.path.getsize(path)
+    print('lanes:', len(glob), 'lanes,', int(start[-1]), 'vertices,', len(views), 'views, survivors',
+          [len(s) for s in survivors], os.path.getsize(path), 'bytes')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(
@@ -1321,7 +1485,8 @@ def main():
     cases = dict(k1=case_k1, kitti=case_kitti_accum, bev=case_bev,
                  bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
                  utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes,
-                 sweeps_edges=case_sweeps_edges, elev_partition=case_elev_partition)
+                 sweeps_edges=case_sweeps_edges, elev_partition=case_elev_partition,
+                 lanes=case_lanes)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
