@@ -49,6 +49,9 @@
 #define C_WAVES (C_THREADS / 64)
 #define C_HIST_WAVES 4            // waves that own a per-wave histogram (cells with more than 64 values)
 #define RGB_CAP 4096              // colour records resident in LDS
+#ifndef C_SLOT_Q
+#define C_SLOT_Q 4                // record slots per round of the tile kernel's coalesced pass 1 and scatter (divides RGB_CAP / C_THREADS)
+#endif
 #define CONTIG_MIN 2560           // tiles above this many records are read thread-contiguously (runs form)
 #define HEAVY_MIN_DEFAULT 2560    // tiles above this many records go to bev_tile_cells_heavy (PCA_BEV_HEAVY_MIN; the
                                   // uniform benchmark's tiles hold ~2000, a dense tile costs the light kernel 4x its neighbours)
@@ -1290,27 +1293,35 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     // contiguous chunk so that runs form (16 records = two cache lines per lane).
     constexpr int RPT = RGB_CAP / C_THREADS;
     constexpr int HALF = RPT / 2;                           // two rounds of loads: bounds the registers in flight
+    constexpr int Q = C_SLOT_Q;                             // slots of one round of the coalesced form
+    static_assert(RPT % Q == 0, "whole rounds");
     const bool contig = (r_hi - r_lo) > CONTIG_MIN;
     const bool div255 = !I64 && a.prm.intensity_div255;
+    // The coalesced form's slot u of thread t is record u * C_THREADS + t: a tile of n records has ceil(n / C_THREADS) slots with
+    // a live lane, the same for the whole workgroup.  Pass 1 and the scatter run in rounds of Q slots and skip (uniform branch) the
+    // rounds past them: a tile of the uniform 200-frame window holds ~1 550 records, 7 of its 16 slots; one of a 1024^2 grid ~100.
+    // (The thread-contiguous form spreads its records over all of a thread's slots.)
+    const uint32_t n_slots = contig ? (uint32_t)RPT : __builtin_amdgcn_readfirstlane((r_hi - r_lo + C_THREADS - 1) / C_THREADS);
     uint32_t kr[RPT], cc[RPT];
-    // the HALF records of one round of thread-record numbers rec(u): all loads first (see recf_raw), then the fields
-    auto load_round = [&](auto rec, uint32_t (&k)[HALF], uint32_t (&c)[HALF], double (&z)[HALF], double (&iv)[HALF]) {
+    // the records of one round of thread-record numbers rec(u) (HALF of them, or Q): all loads first (see recf_raw), then the fields
+    auto load_round = [&](auto rec, auto &k, auto &c, auto &z, auto &iv) {
+        constexpr int N = sizeof(k) / sizeof(k[0]);
         if constexpr (I64) {
 #pragma unroll
-            for (int u = 0; u < HALF; ++u) {
+            for (int u = 0; u < N; ++u) {
                 const uint32_t r = rec(u);
                 k[u] = RUN_NONE; c[u] = 0; z[u] = 0; iv[u] = 0;
                 if (r < r_hi) load_rec<I64>(a, recmap_at(M, L.owner, r), k[u], c[u], z[u], iv[u]);
             }
         } else {
-            uint4 w[HALF];
+            uint4 w[N];
 #pragma unroll
-            for (int u = 0; u < HALF; ++u) {
+            for (int u = 0; u < N; ++u) {
                 const uint32_t r = rec(u);
                 w[u] = recf_raw(a, recmap_at(M, L.owner, r < r_hi ? r : r_lo));      // (r_lo exists: the tile is not empty)
             }
 #pragma unroll
-            for (int u = 0; u < HALF; ++u) {
+            for (int u = 0; u < N; ++u) {
                 recf_fields(w[u], k[u], c[u], z[u], iv[u]);
                 if (!(rec(u) < r_hi)) { k[u] = RUN_NONE; c[u] = 0; }
             }
@@ -1322,14 +1333,17 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     } else if (!contig) {
         // records a workgroup-width apart share a cell only by chance: every record is counted on its own
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            uint32_t k[HALF], c[HALF];
-            double z[HALF], iv[HALF];
-            load_round([&](int u) { return r_lo + (uint32_t)(h * HALF + u) * C_THREADS + threadIdx.x; }, k, c, z, iv);
+        for (int uu = 0; uu < RPT; ++uu) { kr[uu] = RUN_NONE; cc[uu] = 0; }
 #pragma unroll
-            for (int u = 0; u < HALF; ++u) {
-                const int uu = h * HALF + u;
-                kr[uu] = RUN_NONE; cc[uu] = c[u] & 0xffffffu;
+        for (int h = 0; h < RPT / Q; ++h) {
+            if ((uint32_t)(h * Q) >= n_slots) continue;     // (uniform) no lane holds a record in this round or a later one
+            uint32_t k[Q], c[Q];
+            double z[Q], iv[Q];
+            load_round([&](int u) { return r_lo + (uint32_t)(h * Q + u) * C_THREADS + threadIdx.x; }, k, c, z, iv);
+#pragma unroll
+            for (int u = 0; u < Q; ++u) {
+                const int uu = h * Q + u;
+                cc[uu] = c[u] & 0xffffffu;
                 if (k[u] != RUN_NONE) kr[uu] = k[u] | (rec_add(L.S, extra, k[u], c[u], z[u], iv[u], div255) << 8);
             }
         }
@@ -1379,8 +1393,12 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     __syncthreads();
     // ---- pass 2: colours sorted by (cell,set) in LDS, then the medians ----
 #pragma unroll
-    for (int u = 0; u < RPT; ++u)
-        if (kr[u] != 0xffffffffu) s_rgb[L.off[kr[u] & 127u] + (kr[u] >> 8)] = cc[u];
+    for (int h = 0; h < RPT / Q; ++h) {
+        if ((uint32_t)(h * Q) >= n_slots) continue;         // (uniform) a round that pass 1 skipped: every kr is RUN_NONE
+#pragma unroll
+        for (int u = h * Q; u < (h + 1) * Q; ++u)
+            if (kr[u] != 0xffffffffu) s_rgb[L.off[kr[u] & 127u] + (kr[u] >> 8)] = cc[u];
+    }
     __syncthreads();
     DBG_STAMP(16, 4);
     small_cells_bitplanes(L, s_rgb);

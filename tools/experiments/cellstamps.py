@@ -1,4 +1,12 @@
-"""Phase stamps of the light tile kernel (bev_tile_cells) on the headline workload (PCA_BEV_DBG=16): means over all tiles."""
+"""Phase stamps of the light tile kernel (bev_tile_cells) on the headline workload (PCA_BEV_DBG=16): means over all tiles.
+
+Per-phase means, us, one MI355X, four steps each (profiles/bev_tile_slots.txt), before and after pass 1 and the scatter
+went from two rounds of eight record slots per thread to rounds of four that end with the tile's last record:
+
+              span       lifetime    map+pass1  offsets+sort  small cells  wave hist  final+write
+    before    24.5-25.3  19.8-20.4   8.9-9.6    1.0-1.1       7.8-7.9      0.1        1.8-1.9
+    after     23.8-24.9  18.7-19.4   7.7-8.4    0.9           7.9-8.0      0.2        2.0
+"""
 import sys, os, ctypes as C
 os.environ['PCA_BEV_DBG'] = '16'
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
