@@ -535,6 +535,12 @@ void pca_f32_box_decode(const uint32_t *rows /*[n][6]*/, int n, float *box /*[n]
  *     the window, or what pca_bev_bin_range / pca_bev_view_hint left of it}.  G == the device's compute units with a bin range
  *     set: a one-round launch.  0 / -1. */
 int pca_debug_bev_level1(const pca_ctx *ctx, int out[4]);
+/* pca_debug_icp_layout: where a pca_icp_register(n_src, n_tgt) leaves its intermediate results in the caller's workspace
+ *     (host only; nothing is launched).  out[0..11]: byte offsets, from the workspace's base rounded up to 256, of start[0],
+ *     spts[0] (coarse grid), start[1], spts[1] (fine grid), normal, nn_prev, nn_cell, nn_slack, partial, zr_part, state, and the
+ *     total; out[12..15]: the doubles of the state block at which the four slab-range words and the sums of the last pass
+ *     lie, the number of those sums, and the cells per grid (start[] has one word more).  0 / -1 (n < 1, out == NULL). */
+int pca_debug_icp_layout(int32_t n_src, int32_t n_tgt, int64_t out[16]);
 
 /* K1 of pca_kitti_integrate left for the raster that follows it.  The reference's driver integrates a frame and, when its
  * trigger fires, rasterises the window that ends with that frame (run_kitti360_bev_gen.py:186-273): with on = 1, a

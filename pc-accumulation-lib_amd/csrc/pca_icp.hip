@@ -1306,4 +1306,15 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     return icp_read_result(ctx, a, news, IcpOut{T_out, fitness, rmse, iterations}, s);
 }
 
+// diagnostics: where pca_icp_register leaves its intermediate results (host only, nothing is launched)
+int pca_debug_icp_layout(int32_t n_src, int32_t n_tgt, int64_t out[16])
+{
+    if (n_src < 1 || n_tgt < 1 || !out) return -1;
+    const IcpWsLayout L = icp_ws_layout(n_src, n_tgt);
+    const int64_t v[16] = {L.start[0], L.spts[0], L.start[1], L.spts[1], L.normal, L.nn_prev, L.nn_cell, L.nn_slack,
+                           L.partial, L.zr_part, L.state, L.total, ICP_ST_ZR, ICP_ST_SUMS, ICP_NACC, ICP_CELLS};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return 0;
+}
+
 }  // extern "C"
