@@ -97,7 +97,7 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
     uint32_t heavy_hint_known;   // its value when this call was made
     uint32_t *span_hint;  // host-visible word: the points (in units of 1024) this call's level 1 binned, written when the call came
     uint32_t span_hint_known;    // with a bin range; the host sizes the NEXT such launch by it (any piece count gives the same result)
-    int heavy_launched;   // a bev_tile_cells_heavy launch follows (else the light kernel's last workgroup drains the queue)
+    int heavy_launched;   // a bev_tile_cells_heavy launch follows (else a heavy tile is worked off by the light kernel's workgroup that finds it)
     uint32_t *heavy;      // [64 + 32 T]: [0..32) tiles per size class (class 0 = largest), [32] item cursor, then the
                           // classes' tile ids [class][T] -- the queue of bev_tile_cells_heavy, filled by bev_tile_cells
     void *recs;           // RecF / RecD [max_points], tile-ordered; c = r | g<<8 | b<<16 | FLAG_*
@@ -111,7 +111,6 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
 };
 #define HQ_CLASSES 32
 #define HQ_CURSOR 32
-#define HQ_DONE 33              // workgroups of bev_tile_cells that have finished (cells_drain)
 #define HQ_IDS 64
 
 struct Window { int64_t lo, hi, sp, c_lo, c_hi; };
@@ -1153,90 +1152,75 @@ __device__ __forceinline__ void tile_cell_medians32(TileStats &S, uint32_t (*his
                                                     uint32_t r_lo, uint32_t r_hi);
 
 // When the previous call queued no heavy tile the host launches no bev_tile_cells_heavy (an empty launch is 4-6 us of
-// every step on uniform data).  Should tiles be queued nonetheless -- the first dense tile of a sequence -- the LAST
-// workgroup of the light kernel to finish works them off, slowly but exactly: statistics in one pass, then 32-bit
-// histograms cell by cell.  It also tells the host, so that the next call launches the heavy kernel.
+// every step on uniform data).  Should a tile be heavy nonetheless -- the first dense tile of a sequence -- the workgroup
+// that found it works it off right there, slowly but exactly: statistics in one pass, then 16-bit histograms four cells
+// at a time.  It also tells the host, so that the next call launches the heavy kernel (which then writes the real count).
+// Nobody counts the workgroups that have finished: a light tile's workgroup ends with its tile.  (It used to take a ticket
+// from ONE agent-scope word to find the kernel's last workgroup, which then drained the queue alone: 1024 returning atomics
+// on one address in the kernel's last microseconds, each the last thing its workgroup waited for, and needed for nothing
+// when no tile is heavy.)
 template <bool I64, bool BAND = false>
-__device__ __forceinline__ void cells_drain(const BevArgs &a, TileLds &L, unsigned char *s_buf, bool pushed)
+__device__ __forceinline__ void cells_heavy_here(const BevArgs &a, TileLds &L, unsigned char *s_buf, int tile)
 {
     TileStats &S = L.S;
-    if (a.heavy_launched) return;
-    __shared__ uint32_t s_drain_n;
-    if (threadIdx.x == 0) {
-        uint32_t n = 0;
-        if (pushed) __threadfence();                        // this workgroup's queue entry, before it counts as done
-        if (__hip_atomic_fetch_add(&a.heavy[HQ_DONE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-            __threadfence();
-            for (int c = 0; c < HQ_CLASSES; ++c) n += __hip_atomic_load(&a.heavy[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.heavy_hint && n != a.heavy_hint_known) *a.heavy_hint = n;
-        }
-        s_drain_n = n;
-    }
-    __syncthreads();
-    if (s_drain_n == 0) return;
-    __threadfence();
+    // (the host only looks at "!= 0"; without a launch it knows 0: every workgroup with a heavy tile writes the same word)
+    if (threadIdx.x == 0 && a.heavy_hint && a.heavy_hint_known == 0) *a.heavy_hint = 1u;
     const bool extra = a.extra != nullptr;
     const bool div255 = !I64 && a.prm.intensity_div255;
     RecMap &M = *reinterpret_cast<RecMap *>(s_buf);
     uint32_t (*hist)[256] = reinterpret_cast<uint32_t (*)[256]>(s_buf + ((sizeof(RecMap) + 15) & ~(size_t)15));
     static_assert(((sizeof(RecMap) + 15) & ~(size_t)15) + 3 * 256 * 4 <= RGB_CAP * 4, "RecMap + histograms live in the colour buffer");
-    for (int cls = 0; cls < HQ_CLASSES; ++cls) {
-        const uint32_t n_cls = __hip_atomic_load(&a.heavy[cls], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (uint32_t k = 0; k < n_cls; ++k) {
-            const int tile = (int)__hip_atomic_load(&a.heavy[HQ_IDS + (size_t)cls * a.T + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();                                // the staging area of the tile before
-            stats_init(S, C_THREADS);
-            const uint32_t r_hi = recmap_build(M, a, tile, C_THREADS);
-            Run run;
-            run_reset(run, RUN_NONE);
-            const uint32_t per_thread = (r_hi + C_THREADS - 1) / C_THREADS;
-            const uint32_t t_lo = threadIdx.x * per_thread, t_hi = t_lo + per_thread < r_hi ? t_lo + per_thread : r_hi;
-            for (uint32_t r = t_lo; r < t_hi; ++r) {
-                uint32_t kk, c;
-                double z, iv;
-                load_rec<I64>(a, recmap_at(M, a.Gr, r), kk, c, z, iv);
-                if (kk != run.key) {
-                    if (run.key != RUN_NONE) run_flush(S, extra, run);
-                    run_reset(run, kk);
-                }
-                run_add(run, extra, c, z, iv, div255);
-            }
+    __syncthreads();                                // the caller's map of the tile (and its owner table, which the histograms alias)
+    stats_init(S, C_THREADS);
+    const uint32_t r_hi = recmap_build(M, a, tile, C_THREADS);
+    Run run;
+    run_reset(run, RUN_NONE);
+    const uint32_t per_thread = (r_hi + C_THREADS - 1) / C_THREADS;
+    const uint32_t t_lo = threadIdx.x * per_thread, t_hi = t_lo + per_thread < r_hi ? t_lo + per_thread : r_hi;
+    for (uint32_t r = t_lo; r < t_hi; ++r) {
+        uint32_t kk, c;
+        double z, iv;
+        load_rec<I64>(a, recmap_at(M, a.Gr, r), kk, c, z, iv);
+        if (kk != run.key) {
             if (run.key != RUN_NONE) run_flush(S, extra, run);
-            __syncthreads();
-            // medians: four cells (eight fine keys) per pass over the tile's records, 16-bit packed histograms in the
-            // light path's per-wave histogram area; a (cell,set) beyond 65 535 values takes the 32-bit path on its own
-            uint32_t *h16 = &L.whist[0][0][0][0];           // [8 keys][3 channels][128 dwords]
-            for (int c0 = 0; c0 < TCELLS; c0 += 4) {
-                uint32_t any = 0;
-                for (int c = c0; c < c0 + 4; ++c) any += S.cnt[2 * c] + S.cnt[2 * c + 1];
-                if (any == 0) continue;                     // uniform: LDS values
-                for (int k = threadIdx.x; k < 8 * 3 * 128 / 4; k += C_THREADS) reinterpret_cast<uint4 *>(h16)[k] = make_uint4(0, 0, 0, 0);
-                __syncthreads();
-                for (uint32_t r = threadIdx.x; r < r_hi; r += C_THREADS) {
-                    uint32_t kk, v;
-                    load_rec_key_colour<I64>(a, recmap_at(M, a.Gr, r), kk, v);
-                    const uint32_t rel = kk - 2u * (uint32_t)c0;
-                    if (rel >= 8u) continue;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) hist16_add(h16 + (rel * 3 + ch) * 128, (v >> (8 * ch)) & 255u, 1u);
-                }
-                __syncthreads();
-                const int wave = threadIdx.x >> 6;
-                for (int job = wave; job < 4 * 3; job += C_THREADS / 64) {
-                    const int cl = job / 3, ch = job % 3, cell = c0 + cl;
-                    const uint32_t n_p = S.cnt[2 * cell], n_f = S.cnt[2 * cell + 1];
-                    if (n_p + n_f == 0 || n_p > 0xffffu || n_f > 0xffffu) continue;
-                    hist16_medians(S, h16 + ((2 * cl) * 3 + ch) * 128, h16 + ((2 * cl + 1) * 3 + ch) * 128, cell, ch, n_p, n_f);
-                }
-                __syncthreads();
-                for (int cell = c0; cell < c0 + 4; ++cell)
-                    if (S.cnt[2 * cell] > 0xffffu || S.cnt[2 * cell + 1] > 0xffffu)
-                        tile_cell_medians32<I64, C_THREADS>(S, hist, M, a, cell, 0u, r_hi);
-            }
-            __syncthreads();
-            tile_finalize_write<BAND>(a, S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
+            run_reset(run, kk);
         }
+        run_add(run, extra, c, z, iv, div255);
     }
+    if (run.key != RUN_NONE) run_flush(S, extra, run);
+    __syncthreads();
+    // medians: four cells (eight fine keys) per pass over the tile's records, 16-bit packed histograms in the
+    // light path's per-wave histogram area; a (cell,set) beyond 65 535 values takes the 32-bit path on its own
+    uint32_t *h16 = &L.whist[0][0][0][0];           // [8 keys][3 channels][128 dwords]
+    for (int c0 = 0; c0 < TCELLS; c0 += 4) {
+        uint32_t any = 0;
+        for (int c = c0; c < c0 + 4; ++c) any += S.cnt[2 * c] + S.cnt[2 * c + 1];
+        if (any == 0) continue;                     // uniform: LDS values
+        for (int k = threadIdx.x; k < 8 * 3 * 128 / 4; k += C_THREADS) reinterpret_cast<uint4 *>(h16)[k] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        for (uint32_t r = threadIdx.x; r < r_hi; r += C_THREADS) {
+            uint32_t kk, v;
+            load_rec_key_colour<I64>(a, recmap_at(M, a.Gr, r), kk, v);
+            const uint32_t rel = kk - 2u * (uint32_t)c0;
+            if (rel >= 8u) continue;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) hist16_add(h16 + (rel * 3 + ch) * 128, (v >> (8 * ch)) & 255u, 1u);
+        }
+        __syncthreads();
+        const int wave = threadIdx.x >> 6;
+        for (int job = wave; job < 4 * 3; job += C_THREADS / 64) {
+            const int cl = job / 3, ch = job % 3, cell = c0 + cl;
+            const uint32_t n_p = S.cnt[2 * cell], n_f = S.cnt[2 * cell + 1];
+            if (n_p + n_f == 0 || n_p > 0xffffu || n_f > 0xffffu) continue;
+            hist16_medians(S, h16 + ((2 * cl) * 3 + ch) * 128, h16 + ((2 * cl + 1) * 3 + ch) * 128, cell, ch, n_p, n_f);
+        }
+        __syncthreads();
+        for (int cell = c0; cell < c0 + 4; ++cell)
+            if (S.cnt[2 * cell] > 0xffffu || S.cnt[2 * cell + 1] > 0xffffu)
+                tile_cell_medians32<I64, C_THREADS>(S, hist, M, a, cell, 0u, r_hi);
+    }
+    __syncthreads();
+    tile_finalize_write<BAND>(a, S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
 }
 
 #define DBG_STAMP(bit, slot) do { if ((a.dbg & (bit)) && threadIdx.x == 0 && tile < 1024) g_dbg_stamps[tile][slot] = wall_clock64(); } while (0)
@@ -1281,9 +1265,9 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     static_assert(sizeof(RecMap) <= sizeof(s_buf), "RecMap aliases the colour buffer");
     stats_init(L.S, C_THREADS);
     const uint32_t r_lo = 0, r_hi = recmap_build(M, a, tile, C_THREADS, L.owner);
-    if (r_hi > (uint32_t)a.heavy_min) {                     // bev_tile_cells_heavy's
-        if (threadIdx.x == 0) heavy_push(a, tile, r_hi);
-        cells_drain<I64, BAND>(a, L, s_buf, true);
+    if (r_hi > (uint32_t)a.heavy_min) {                     // bev_tile_cells_heavy's, if one follows
+        if (a.heavy_launched) { if (threadIdx.x == 0) heavy_push(a, tile, r_hi); }
+        else cells_heavy_here<I64, BAND>(a, L, s_buf, tile);
         return;
     }
 
@@ -1412,7 +1396,6 @@ __device__ __forceinline__ void bev_tile_cells_body(const BevArgs &a)
     }
     DBG_STAMP(16, 6);
     tile_finalize_write<BAND>(a, L.S, reinterpret_cast<double(*)[TCELLS]>(s_buf), tile, C_THREADS);
-    cells_drain<I64, BAND>(a, L, s_buf, false);
     if ((a.dbg & 16) && threadIdx.x == 0 && tile < 1024) {
         g_dbg_stamps[tile][0] = t_begin; g_dbg_stamps[tile][1] = wall_clock64(); g_dbg_stamps[tile][2] = r_hi - r_lo;
         uint32_t big = 0;
