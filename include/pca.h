@@ -237,6 +237,9 @@ int pca_mark_dynamic(pca_ctx *ctx, const pca_store *store, const int64_t *frame_
  *     [slot_begin, slot_end): of all points in one voxel floor(xyz / voxel_size) the first in store order (the
  *     oldest observation) stays.  Segments are compacted in place, order-preserving; frame_off[slot_begin+1 ..
  *     slot_end] is rewritten.  slot_end must be the last used slot (later segments are not moved).
+ *     The key holds 21 bits per axis: voxel indices are clamped to [-2^20, 2^20) per axis, i.e. +-2^20 * voxel_size metres
+ *     (+-inf included).  Every point beyond that shares the boundary voxel of its side -- with the points that really lie in
+ *     it -- and only the first of them stays.
  * ------------------------------------------------------------------------------------------------ */
 int64_t pca_voxel_dedup_workspace_bytes(int64_t max_points, int n_slots);
 int pca_voxel_dedup(pca_ctx *ctx, const pca_store *store, int64_t *frame_off /*dev*/, int slot_begin, int slot_end,

@@ -516,7 +516,9 @@ class DeviceStore:
 
     def voxel_dedup(self, voxel_size):
         """Opt-in (no reference counterpart): of all live points in one voxel floor(xyz / voxel_size) only the first
-        in store order (the oldest observation) stays; frames are compacted in place, order-preserving."""
+        in store order (the oldest observation) stays; frames are compacted in place, order-preserving.
+        Voxel indices are clamped to [-2^20, 2^20) per axis (+-2^20 * voxel_size metres): the points beyond that share the
+        boundary voxel of their side, of which only the first stays."""
         if self.n_frames == 0:
             return
         self.flush_pending()
