@@ -608,6 +608,47 @@ int pca_host_d2h_async(pca_ctx *ctx, const void *dev, void *pinned, int64_t byte
 int pca_host_d2h_wait(pca_ctx *ctx, int ticket);
 
 /* ------------------------------------------------------------------------------------------------
+ * KZ: the gzip container of a sample, compressed on the device.  Replaces the gzip.open(...).write(pickle.dumps(obj)) of
+ * sem_pc_accum.py:280-294 for the bytes that live on the device (the fp16 planes, 2.75 MB of a sample's pickle); what
+ * comes out is read by the unchanged read_compressed_pickle (:296-302) and inflates to the very bytes the host would have
+ * pickled.  Opt-in (pca_amd/writer.py, codec='device'); no reference counterpart for the encoder itself.
+ *
+ * pca_deflate_chunks   src: device bytes; chunk_table: device, n_chunks entries (offset into src, length 0 ..
+ *     PCA_DEFLATE_CHUNK_MAX; any alignment, odd lengths too).  Every chunk becomes one self-contained, byte-aligned piece of
+ *     a raw DEFLATE stream: a non-final fixed-Huffman block (BTYPE 01) of literals and of matches of length 3 .. 128 at distance 1
+ *     or 2 -- byte runs and half-word runs, split every 128 bytes of the chunk -- that never reach before the chunk's first byte, then an empty non-final stored block
+ *     (the sync-flush marker 00 00 ff ff).  Pieces therefore concatenate bytewise, with each other and with stored blocks.
+ *     A chunk of n bytes gives at most PCA_DEFLATE_BOUND(n) bytes (no stored-block fallback: random bytes grow by 1/8).
+ *     out_sizes[c]: bytes of piece c; out_crcs[c]: CRC-32 (the gzip polynomial, reflected) of the chunk's own bytes;
+ *     out: the pieces back to back in table order, piece c at the sum of the sizes before it (room for the sum of the
+ *     bounds); workspace: pca_deflate_workspace_bytes(n_chunks), device.  All outputs are device memory.
+ *     Stream and lifetime rules are those of pca_host_d2h_async: the kernels run on the context's side stream behind
+ *     everything enqueued on `stream` so far, and the return value is a ticket for pca_host_d2h_wait (or -1).  A
+ *     pca_host_d2h_async issued after it copies the results behind the kernels.  src, the table, the outputs and the
+ *     workspace are to be left alone until the ticket (or a later one) has been waited for.
+ * pca_host_crc32_combine   CRC-32 of A || B from crc(A), crc(B) and the length of B (GF(2) arithmetic, no data pass;
+ *     zlib's crc32_combine, which Python's zlib module does not expose).  len_b < 0: returns 0.
+ * pca_host_gzip_assemble   one gzip member from n_pieces pieces in order: the 10-byte header, the pieces, a final empty
+ *     fixed block, CRC-32 and ISIZE of the whole uncompressed stream.  raw_bytes[k] < 0: piece[k] is piece_bytes[k] plain
+ *     bytes (a fragment of the pickle that lives on the host), written as non-final stored blocks of at most 65 535 bytes
+ *     and summed here; raw_bytes[k] >= 0: piece[k] is a byte-aligned piece of a DEFLATE stream without a final block (one
+ *     or more pieces of pca_deflate_chunks) that inflates to raw_bytes[k] bytes whose CRC-32 is crc[k].  Zero-length
+ *     pieces are legal.  Returns the member's length, -1 for bad arguments, -2 if out_cap is too small (20 bytes, every
+ *     piece, and 5 bytes per stored block).  Host only.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_DEFLATE_CHUNK_MAX 32768
+#define PCA_DEFLATE_MAX_CHUNKS (1 << 20)
+#define PCA_DEFLATE_BOUND(n) ((9 * (int64_t)(n) + 7) / 8 + 16)
+typedef struct { int64_t offset; int32_t length; int32_t reserved; } pca_deflate_chunk;
+int64_t pca_deflate_workspace_bytes(int64_t n_chunks);
+int pca_deflate_chunks(pca_ctx *ctx, const void *src /*dev*/, const pca_deflate_chunk *chunk_table /*dev*/, int64_t n_chunks,
+                       void *out /*dev*/, uint32_t *out_sizes /*dev*/, uint32_t *out_crcs /*dev*/, void *workspace /*dev*/,
+                       void *stream);
+uint32_t pca_host_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
+int64_t pca_host_gzip_assemble(int32_t n_pieces, const void *const *piece, const int64_t *piece_bytes, const int64_t *raw_bytes,
+                               const uint32_t *crc, void *out, int64_t out_cap);
+
+/* ------------------------------------------------------------------------------------------------
  * Host helper (no device work): the accumulator's pose track -- the per-frame bookkeeping integrate() does on Python
  * lists in the reference.  Replaces sem_pc_accum.py:156-165 (update_poses), :185-209 (remove_observations), :211-228
  * (comp_incr_path_dist), :404-415 (dist) and, for runners that replay it, the sample trigger of

@@ -36,6 +36,11 @@ class _PendingCopy:
             pass
 
 
+def _writer():
+    from pca_amd import writer
+    return writer
+
+
 class LazyBev(dict):
     """The reference's BEV dict whose plane arrays are still on their way from the device: the fp16 D2H copy was
     enqueued on a side stream into pinned memory; the first access waits for THAT copy only and fills the dict in.
@@ -51,6 +56,14 @@ class LazyBev(dict):
         super().__init__()
         self._pending = (host, index, event, trajs, gt_lanes)
         self._error = None
+        # while the writer's device codec is selected (pca_amd.writer): (the device planes this sample is part of, its index), so that it
+        # can still be compressed there after it -- or a sibling that shares the copy -- has been filled in; the writer
+        # drops the reference once the compression has been waited for
+        self._dev = None
+        self._host_planes = None
+        keep = getattr(event, 'keep', None)
+        if keep and _writer().device_codec_selected():
+            self._dev = (keep[0], index)
         self._zero_copy = LazyBev._live[0] < LazyBev.MAX_PINNED_LIVE
         if self._zero_copy:
             import weakref
@@ -74,6 +87,9 @@ class LazyBev(dict):
             planes = host[index].numpy()
             if not self._zero_copy:
                 planes = np.array(planes)
+            if self._dev is not None:            # the device codec will write the DEVICE planes: no silent edits of the copy
+                planes.flags.writeable = False
+                self._host_planes = planes
             if gt_lanes is not None and not isinstance(gt_lanes, list):     # pca_amd.lanes.PendingLanes: decoded now
                 gt_lanes = gt_lanes.resolve()
             dict.update(self, SemBEVGenerator.pack_bev(planes, trajs[0], trajs[1], trajs[2], gt_lanes))

@@ -437,22 +437,34 @@ extern "C" int pca_host_stage_h2d(int n, const void *const *src, void *const *pi
 // (In Python this was a stream context, wait_stream, copy_, an Event and record_stream per sample: 0.04 ms of the
 // unchanged driver's 0.24 ms step.)
 // ---------------------------------------------------------------------------------------------
+// internal (also pca_deflate.hip): the side stream exists and waits for what `after` holds so far; then, behind what the
+// caller has put on it, the next completion event of the ring -- the ticket
+int pca_side_begin(pca_ctx *ctx, hipStream_t after)
+{
+    if (!ctx->d2h_stream) {
+        PCA_CHECK(ctx, hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
+        PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->d2h_go, hipEventDisableTiming));
+    }
+    PCA_CHECK(ctx, hipEventRecord(ctx->d2h_go, after));
+    PCA_CHECK(ctx, hipStreamWaitEvent(ctx->d2h_stream, ctx->d2h_go, 0));
+    return 0;
+}
+int pca_side_ticket(pca_ctx *ctx)
+{
+    const uint32_t k = ctx->d2h_next++ & 63u;
+    if (!ctx->d2h_done[k]) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->d2h_done[k], hipEventDisableTiming));
+    PCA_CHECK(ctx, hipEventRecord(ctx->d2h_done[k], ctx->d2h_stream));
+    return (int)k;
+}
+
 extern "C" int pca_host_d2h_async(pca_ctx *ctx, const void *dev, void *pinned, int64_t bytes, void *stream)
 {
     if (!ctx) return -1;
     if (!dev || !pinned || bytes < 0) { ctx->err = "d2h_async: bad arguments"; return -1; }
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d2h_stream) {
-        PCA_CHECK(ctx, hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
-        PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->d2h_go, hipEventDisableTiming));
-    }
-    const uint32_t k = ctx->d2h_next++ & 63u;
-    if (!ctx->d2h_done[k]) PCA_CHECK(ctx, hipEventCreateWithFlags(&ctx->d2h_done[k], hipEventDisableTiming));
-    PCA_CHECK(ctx, hipEventRecord(ctx->d2h_go, (hipStream_t)stream));
-    PCA_CHECK(ctx, hipStreamWaitEvent(ctx->d2h_stream, ctx->d2h_go, 0));
+    if (pca_side_begin(ctx, (hipStream_t)stream)) return -1;
     if (bytes > 0) PCA_CHECK(ctx, hipMemcpyAsync(pinned, dev, (size_t)bytes, hipMemcpyDeviceToHost, ctx->d2h_stream));
-    PCA_CHECK(ctx, hipEventRecord(ctx->d2h_done[k], ctx->d2h_stream));
-    return (int)k;
+    return pca_side_ticket(ctx);
 }
 
 // Waits for the copy of `ticket` (a ticket older than 64 copies waits for a later copy of the same stream: still after its own).

@@ -1,19 +1,264 @@
 """Output writer: the reference writes each BEV sample as gzip(pickle(dict)) synchronously
 (sem_pc_accum.py:280-294); once a sample costs < 1 ms on the GPU that dominates.  AsyncBevWriter does the device->host
-copy, pickling and compression on worker threads.  Same container, same dict schema (README.md:60-99 of the reference)."""
+copy, pickling and compression on worker threads.  Same container, same dict schema (README.md:60-99 of the reference).
+
+codec='device' (opt-in; PCA_WRITER_CODEC=device for the shared writer) leaves the per-byte pass over the planes on the GPU:
+the pickle of a sample is laid out from zero-filled stand-ins, the 15 plane payloads are located in it, and those byte
+ranges of the device planes are compressed there (pca_deflate_chunks: fixed-Huffman pieces that concatenate bytewise).  The
+worker threads then only splice: pickle fragments from the host as stored blocks, device pieces as they are, one gzip
+member (pca_host_gzip_assemble).  The file inflates to exactly pickle.dumps(dict(bev))."""
 import atexit
+import ctypes as C
 import gzip
 import os
 import pickle
+import pickletools
 import queue
 import threading
 
 import numpy as np
 
+DEFLATE_CHUNK_MAX = 32768
+DEFLATE_CHUNK_DTYPE = np.dtype([('offset', '<i8'), ('length', '<i4'), ('reserved', '<i4')])      # pca_deflate_chunk
+_BYTES_OPS = ('SHORT_BINBYTES', 'BINBYTES', 'BINBYTES8', 'BYTEARRAY8')
+_BYTES_HEADER = {'SHORT_BINBYTES': 2, 'BINBYTES': 5, 'BINBYTES8': 9, 'BYTEARRAY8': 9}
+_PLANE_GROUPS = ((0, 1), (1, 1), (2, 3), (5, 1), (6, 1))      # pack_bev: road p[0], intensity p[1], rgb p[2:5], dynamic p[5], elevation p[6]
+
+
+_device_writers = [0]
+
+
+def device_codec_selected():
+    """True while a writer with the device codec is open or the shared writer is to be one: a LazyBev made meanwhile keeps a
+    reference to its device planes (dropped by the writer once they have been compressed).  A writer stays open until its
+    close() has run, whether or not that raised: its worker threads keep a writer that was merely dropped alive."""
+    return _device_writers[0] > 0 or os.environ.get('PCA_WRITER_CODEC', 'host') == 'device'
+
+
+def deflate_bound(n):
+    """Most bytes pca_deflate_chunks makes of a chunk of n (PCA_DEFLATE_BOUND)."""
+    return (9 * n + 7) // 8 + 16
+
+
+def plane_payloads(px):
+    """(byte offset, length) inside one [21,px,px] float16 sample of the 15 arrays of pack_bev, in the dict's order."""
+    cell = px * px * 2
+    return [((7 * s + k0) * cell, k * cell) for s in range(3) for k0, k in _PLANE_GROUPS]
+
+
+def chunk_table(payloads, base=0, chunk_max=DEFLATE_CHUNK_MAX):
+    """Cuts every payload into chunks of at most chunk_max bytes: (table as DEFLATE_CHUNK_DTYPE records, first chunk of
+    each payload with the total appended)."""
+    rows, first = [], []
+    for off, length in payloads:
+        first.append(len(rows))
+        rows += [(base + off + at, min(chunk_max, length - at), 0) for at in range(0, length, chunk_max)]
+    first.append(len(rows))
+    return np.array(rows, dtype=DEFLATE_CHUNK_DTYPE), first
+
+
+def _arrays_in_pickle_order(obj, out):
+    if isinstance(obj, np.ndarray):
+        out.append(obj)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _arrays_in_pickle_order(v, out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _arrays_in_pickle_order(v, out)
+    return out
+
+
+def stand_in_sample(px, trajs_present, trajs_future, trajs_full, gt_lanes=None, extra=None):
+    """The sample's dict with zero-filled stand-ins for the plane arrays: same shapes, dtype and views as pack_bev makes
+    them.  Returns (dict, the zero block the stand-ins are views of)."""
+    from bev_generator.sem_bev import SemBEVGenerator
+    zeros = np.zeros((21, px, px), dtype=np.float16)
+    out = SemBEVGenerator.pack_bev(zeros, trajs_present, trajs_future, trajs_full, gt_lanes)
+    for k, v in (extra or {}).items():
+        if k not in out:
+            out[k] = v
+    return out, zeros
+
+
+def locate_payloads(blob, stand_in, zeros):
+    """Where the plane payloads lie in `blob` = pickle.dumps(stand_in): [(start in blob, nbytes)] in pack_bev's order, or
+    None if the pickle's byte-string ops do not match the dict's arrays one for one (the sample then takes the host codec).
+    The layout of a pickle does not depend on array contents, so the same ranges hold for the real sample.  Left out on
+    both sides: the one-byte marker b'b' of numpy's reconstructor and empty payloads, which pickle may memoise."""
+    arrays = [a for a in _arrays_in_pickle_order(stand_in, []) if a.nbytes]
+    if any(a.nbytes == 1 or a.dtype.hasobject for a in arrays):
+        return None
+    ops = [(op.name, arg, pos) for op, arg, pos in pickletools.genops(blob) if op.name in _BYTES_OPS and len(arg) and bytes(arg) != b'b']
+    if len(ops) != len(arrays):
+        return None
+    found = []
+    for (name, arg, pos), a in zip(ops, arrays):
+        if len(arg) != a.nbytes:
+            return None
+        if a.base is zeros or a is zeros:
+            found.append((pos + _BYTES_HEADER[name], a.nbytes))
+    if [n for _, n in found] != [n for _, n in plane_payloads(zeros.shape[-1])]:
+        return None
+    return found
+
+
+class _Layout:
+    """What depends on px alone: payload ranges, their chunks, the output's capacity -- all per sample."""
+    _by_px = {}
+
+    def __init__(self, px):
+        self.px = px
+        self.sample_bytes = 21 * px * px * 2
+        self.payloads = plane_payloads(px)
+        self.table, self.first = chunk_table(self.payloads)
+        self.n = len(self.table)
+        self.cap = int(sum(deflate_bound(int(l)) for l in self.table['length']))
+        self.dev_tables = {}                 # (device index, samples) -> device copy of the table of a [samples,21,px,px] block
+
+    @classmethod
+    def get(cls, px):
+        if px not in cls._by_px:
+            cls._by_px[px] = _Layout(px)
+        return cls._by_px[px]
+
+    def device_table(self, device, k):
+        import torch
+        key = (device.index, k)
+        if key not in self.dev_tables:
+            t = np.tile(self.table, k)
+            t['offset'] += np.repeat(np.arange(k, dtype=np.int64) * self.sample_bytes, self.n)
+            self.dev_tables[key] = torch.from_numpy(t.view(np.uint8).copy()).to(device)
+        return self.dev_tables[key]
+
+
+class _DeviceJob:
+    """The compression of ALL samples of one [k,21,px,px] block in flight on the context's side stream: one launch of the
+    kernels, then ONE copy of (sizes, crcs, bytes).  The samples of a generate_bev_many share it.  Holds planes, table,
+    outputs and workspace until the copy has been waited for."""
+
+    def __init__(self, planes):
+        import weakref
+
+        import torch
+        from . import _lib
+        assert planes.is_contiguous() and planes.dtype == torch.float16 and planes.dim() == 4 and planes.shape[1] == 21
+        self.layout = lay = _Layout.get(int(planes.shape[-1]))
+        self.ctx = ctx = _lib.Context.get(planes.device)
+        self.planes_ref = weakref.ref(planes)
+        k = int(planes.shape[0])
+        self.n = n = k * lay.n
+        table = lay.device_table(planes.device, k)
+        ws = torch.empty(int(ctx.lib.pca_deflate_workspace_bytes(n)), dtype=torch.uint8, device=planes.device)
+        dev = torch.empty(8 * n + k * lay.cap, dtype=torch.uint8, device=planes.device)
+        self.host = torch.empty(8 * n + k * lay.cap, dtype=torch.uint8, pin_memory=True)
+        p = dev.data_ptr()
+        rc = ctx.lib.pca_deflate_chunks(ctx.h, planes.data_ptr(), table.data_ptr(), n, p + 8 * n, p, p + 4 * n, ws.data_ptr(),
+                                        ctx.stream())
+        if rc < 0:
+            ctx.check(rc)
+        # (rc is the ticket of the kernels alone, for callers that leave the pieces on the device.  The copy below runs behind
+        # them on the same side stream, so its ticket covers both and is the only one waited for; the ring of 64 completion
+        # events simply moves on by two per job -- an older ticket waits for a later event of the same stream.)
+        self.ticket = ctx.lib.pca_host_d2h_async(ctx.h, p, self.host.data_ptr(), dev.numel(), ctx.stream())
+        if self.ticket < 0:
+            ctx.check(self.ticket)
+        self.keep = (planes, table, ws, dev)
+
+    def wait(self):
+        """On the thread that talks to HIP: the results are in `host`, the device blocks go back."""
+        if self.keep is not None:
+            self.ctx.check(self.ctx.lib.pca_host_d2h_wait(self.ctx.h, self.ticket))
+            self.keep = None
+            self.ctx.poll_status()
+
+    def results(self, index):
+        """(sizes, crcs, bytes) of the chunks of sample `index`."""
+        n, m = self.n, self.layout.n
+        h = self.host.numpy()
+        sizes, crcs = h[:4 * n].view(np.uint32), h[4 * n:8 * n].view(np.uint32)
+        at = 8 * n + int(sizes[:index * m].sum(dtype=np.int64))
+        return sizes[index * m:(index + 1) * m], crcs[index * m:(index + 1) * m], h[at:]
+
+    def __del__(self):
+        try:
+            if self.keep is not None:
+                self.ctx.lib.pca_host_d2h_wait(self.ctx.h, self.ticket)
+        except Exception:                    # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def gzip_assemble(pieces):
+    """pieces: [(uint8 array, raw_bytes, crc)] -- raw_bytes < 0: plain bytes (stored blocks), else a deflate piece that
+    inflates to raw_bytes bytes of that CRC-32.  Returns the gzip member as a uint8 array (pca_host_gzip_assemble)."""
+    from . import _lib
+    lib = _lib.load()
+    n = len(pieces)
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a, _, _ in pieces]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    nbytes = np.array([a.size for a in arrs], dtype=np.int64)
+    raw = np.array([r for _, r, _ in pieces], dtype=np.int64)
+    crc = np.array([c for _, _, c in pieces], dtype=np.uint32)
+    need = 20 + int(nbytes.sum()) + 5 * int(sum((int(b) + 65534) // 65535 for b, r in zip(nbytes, raw) if r < 0))
+    out = np.empty(need, dtype=np.uint8)
+    got = lib.pca_host_gzip_assemble(n, C.addressof(ptrs), nbytes.ctypes.data, raw.ctypes.data, crc.ctypes.data, out.ctypes.data, need)
+    if got < 0:
+        raise RuntimeError(f'pca_host_gzip_assemble failed ({got})')
+    return out[:got]
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    from . import _lib
+    return int(_lib.load().pca_host_crc32_combine(int(crc_a), int(crc_b), int(len_b)))
+
+
+def splice_sample(blob, found, layout, sizes, crcs, data):
+    """The gzip member of a sample: `blob` (the stand-in's pickle) between the payloads `found`, the device pieces in their
+    place.  sizes / crcs / data: what pca_deflate_chunks left for the layout's chunk table."""
+    host = np.frombuffer(blob, dtype=np.uint8)
+    ends = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
+    lengths = layout.table['length']
+    pieces, at = [], 0
+    for k, (start, nbytes) in enumerate(found):
+        pieces.append((host[at:start], -1, 0))
+        c0, c1 = layout.first[k], layout.first[k + 1]
+        crc = 0
+        for c in range(c0, c1):
+            crc = crc32_combine(crc, crcs[c], lengths[c])
+        pieces.append((data[ends[c0]:ends[c1]], nbytes, crc))
+        at = start + nbytes
+    pieces.append((host[at:], -1, 0))
+    return gzip_assemble(pieces)
+
+
+class _Item:
+    """One sample on its way through the writer.  job is None: the host codec takes it (bev is a plain dict by the time a
+    worker sees it, unless it is the device_only form).  Else: sample `index` of that device job, meta = what
+    stand_in_sample needs (filled in when the job has been waited for)."""
+    __slots__ = ('bev', 'filename', 'write_dir', 'job', 'index', 'meta')
+
+    def __init__(self, bev, filename, write_dir, job=None, index=0):
+        self.bev, self.filename, self.write_dir, self.job, self.index, self.meta = bev, filename, write_dir, job, index, None
+
 
 class AsyncBevWriter:
 
-    def __init__(self, n_threads=4, compresslevel=9, max_pending=64):
+    def __init__(self, n_threads=4, compresslevel=9, max_pending=64, codec='host'):
+        if codec not in ('host', 'device'):
+            raise ValueError(f"codec must be 'host' or 'device', not {codec!r}")
+        self.codec = codec
+        # device codec: samples written from device pieces / samples that came from the device but were written by the host
+        # codec all the same (pickle without the expected byte strings, a LazyBev made before the codec was selected or
+        # submitted a second time, plane arrays replaced after the sample filled in)
+        self.device_written = 0
+        self.fallbacks = 0
+        self._lock = threading.Lock()
+        self._refill = []                    # samples a worker handed back: filled in on the submitting thread, then host codec
+        self._jobs = {}                      # id(planes block) -> its device job, while the block lives
+        self._parked = None
+        self._open = True
+        if codec == 'device':
+            _device_writers[0] += 1
         self.q = queue.Queue(maxsize=max_pending)
         self.compresslevel = compresslevel
         self.errors = []
@@ -35,54 +280,157 @@ class AsyncBevWriter:
                 out[k] = v
         return out
 
-    @staticmethod
-    def _plain(bev):
-        return dict(bev) if type(bev) is not dict else bev          # LazyBev: waits for its copy here, off the main thread
+    def _write_host(self, it):
+        blob = pickle.dumps(self._to_host(it.bev))
+        with gzip.open(os.path.join(it.write_dir, f'{it.filename}.gz'), 'wb', compresslevel=self.compresslevel) as f:
+            f.write(blob)
+
+    def _write_device(self, it):
+        stand_in, zeros = stand_in_sample(it.job.layout.px, *it.meta)
+        blob = pickle.dumps(stand_in)
+        found = locate_payloads(blob, stand_in, zeros)
+        if found is None:                    # back to the submitting thread: it fills the sample in, the host codec writes it
+            with self._lock:
+                self.fallbacks += 1
+                self._refill.append(it)
+            return
+        member = splice_sample(blob, found, it.job.layout, *it.job.results(it.index))
+        with open(os.path.join(it.write_dir, f'{it.filename}.gz'), 'wb') as f:
+            f.write(memoryview(member))
+        with self._lock:
+            self.device_written += 1
 
     def _work(self):
         while True:
-            job = self.q.get()
-            if job is None:
+            it = self.q.get()
+            if it is None:
                 return
-            bev, filename, write_dir = job
             try:
-                os.makedirs(write_dir, exist_ok=True)
-                blob = pickle.dumps(self._plain(self._to_host(bev)))
-                with gzip.open(os.path.join(write_dir, f'{filename}.gz'), 'wb', compresslevel=self.compresslevel) as f:
-                    f.write(blob)
+                os.makedirs(it.write_dir, exist_ok=True)
+                if it.job is not None:
+                    self._write_device(it)
+                else:
+                    self._write_host(it)
             except Exception as e:              # reported by close(); the reference prints IOErrors and goes on
                 self.errors.append(e)
             finally:
                 self.q.task_done()
 
+    @staticmethod
+    def _planes_intact(bev):
+        """A LazyBev that has filled in: do its plane entries still show the arrays the copy landed in?"""
+        host = getattr(bev, '_host_planes', None)
+        if host is None:
+            return False
+        px = host.shape[-1]
+        keys = [f'{name}_{s}' for s in ('present', 'future', 'full') for name in ('road', 'intensity', 'rgb', 'dynamic', 'elevation')]
+        for key, (off, nbytes) in zip(keys, plane_payloads(px)):
+            v = dict.get(bev, key)
+            if not isinstance(v, np.ndarray) or v.dtype != np.float16 or v.nbytes != nbytes or not v.flags.c_contiguous \
+                    or v.ctypes.data != host.ctypes.data + off or v.flags.writeable:
+                return False
+        return True
+
+    def _device_source(self, bev):
+        """(planes block [k,21,px,px] on the device, index of the sample in it), or None: the host codec takes the sample."""
+        if hasattr(bev, '_pending'):         # LazyBev: it holds its device planes while the device codec is selected
+            dev = getattr(bev, '_dev', None)
+            if dev is None and bev._pending is not None:     # made before the codec was selected: its copy may still hold them
+                keep = getattr(bev._pending[2], 'keep', None)
+                dev = (keep[0], bev._pending[1]) if keep else None
+            if dev is None or not dev[0].is_cuda or (bev._pending is None and not self._planes_intact(bev)):
+                return None
+            planes = dev[0]
+            return (planes if planes.dim() == 4 else planes.view((1, ) + tuple(planes.shape))), dev[1]
+        planes = bev['planes_f16']
+        if not planes.is_cuda or planes.dim() != 3 or planes.shape[0] != 21 or planes.shape[1] != planes.shape[2]:
+            return None
+        return planes.contiguous().view((1, ) + tuple(planes.shape)), 0
+
+    def _device_job(self, planes):
+        """The job that compresses `planes`: the one a sibling sample started, or a new one."""
+        job = self._jobs.get(id(planes))
+        if job is None or job.planes_ref() is not planes:
+            self._jobs = {k: j for k, j in self._jobs.items() if j.planes_ref() is not None}
+            job = self._jobs[id(planes)] = _DeviceJob(planes)
+        return job
+
     def submit(self, bev, filename, write_dir):
         """Same arguments as SemanticPointCloudAccumulator.write_compressed_pickle.  A sample whose planes are still on
         their way from the device (LazyBev) is parked; it is filled in -- on THIS thread, the one that talks to HIP -- and
         queued when the next sample arrives (its copy has long finished by then) or at flush / close.  The worker threads
-        only pickle and compress."""
+        only pickle and compress.  With the device codec the compression of the sample's block of planes is enqueued
+        here, on the side stream the copy uses (once per block: the samples of a generate_bev_many share it), and the
+        sample is parked with it; the worker threads then only assemble and write."""
         self._release_parked()
-        if getattr(bev, '_pending', None) is not None:
-            self._parked = (bev, filename, write_dir)
-            return
+        self._take_refills()
+        from_device = hasattr(bev, '_pending') or (type(bev) is dict and 'planes_f16' in bev)
         if type(bev) is dict and 'planes_f16' in bev:       # snapshot: the caller may reuse the device buffer
             bev = dict(bev, planes_f16=bev['planes_f16'].clone())
-        self.q.put((bev, filename, write_dir))
+        if self.codec == 'device' and from_device:
+            src = self._device_source(bev)
+            if src is not None:
+                self._parked = _Item(bev, filename, write_dir, self._device_job(src[0]), src[1])
+                return
+            with self._lock:
+                self.fallbacks += 1
+        if getattr(bev, '_pending', None) is not None:
+            self._parked = _Item(bev, filename, write_dir)
+            return
+        self.q.put(_Item(bev if type(bev) is dict else dict(bev), filename, write_dir))
+
+    @staticmethod
+    def _meta(bev):
+        """Everything of the sample but its planes: (trajs_present, trajs_future, trajs_full, gt_lanes, extra keys)."""
+        pending = getattr(bev, '_pending', None)
+        if pending is not None:
+            trajs, gt_lanes = pending[3], pending[4]
+            if gt_lanes is not None and not isinstance(gt_lanes, list):      # pca_amd.lanes.PendingLanes: decoded now
+                gt_lanes = gt_lanes.resolve()
+            return trajs[0], trajs[1], trajs[2], gt_lanes, None
+        return (bev['trajs_present'], bev['trajs_future'], bev['trajs_full'], bev.get('gt_lanes'),
+                {k: v for k, v in bev.items() if k != 'planes_f16'})
 
     def _release_parked(self):
-        parked, self._parked = getattr(self, '_parked', None), None
-        if parked is not None:
-            self.q.put((dict(parked[0]), parked[1], parked[2]))
+        it, self._parked = self._parked, None
+        if it is None:
+            return
+        if it.job is not None:
+            it.job.wait()
+            it.meta = self._meta(it.bev)
+            if getattr(it.bev, '_dev', None) is not None:
+                it.bev._dev = None           # compressed: the sample lets go of its device planes
+        else:
+            it.bev = dict(it.bev)
+        self.q.put(it)
+
+    def _take_refills(self):
+        """Samples the workers could not splice: filled in here, on the submitting thread, and queued for the host codec."""
+        with self._lock:
+            back, self._refill = self._refill, []
+        for it in back:
+            self.q.put(_Item(it.bev if type(it.bev) is dict else dict(it.bev), it.filename, it.write_dir))
+        return len(back)
 
     def flush(self):
         self._release_parked()
         self.q.join()
+        while self._take_refills():
+            self.q.join()
 
     def close(self):
-        self.flush()
-        for _ in self.threads:
-            self.q.put(None)
-        for t in self.threads:
-            t.join()
+        if not self._open:
+            return
+        try:
+            self.flush()
+        finally:                             # whatever flush raised: the writer is closed and the codec no longer selected by it
+            for _ in self.threads:
+                self.q.put(None)
+            for t in self.threads:
+                t.join()
+            if self.codec == 'device':
+                _device_writers[0] -= 1
+            self._open = False
         if self.errors:
             raise self.errors[0]
 
@@ -95,7 +443,8 @@ def shared_writer():
     joined at interpreter exit, so every file is on disk when the unchanged driver returns."""
     global _shared
     if _shared is None:
-        _shared = AsyncBevWriter(n_threads=int(os.environ.get('PCA_WRITER_THREADS', '4')))
+        _shared = AsyncBevWriter(n_threads=int(os.environ.get('PCA_WRITER_THREADS', '4')),
+                                 codec=os.environ.get('PCA_WRITER_CODEC', 'host'))
         atexit.register(_shared.close)
     return _shared
 
