@@ -120,6 +120,13 @@ int pca_kitti_project_sample_filter_ex(pca_ctx *ctx, const pca_kitti_frame *fram
  *     Replaces nuscenes_oracle_sem_pc_accum.py:457-501 and datasets/nuscenes_utils.py:181-214 ('nearest').
  *     pc: dev [n,7] f64 rows x,y,z,intensity,u,v,inst;  cam_idx: dev [n] int64 (-1: on no image);
  *     imgs: dev [ncam,H,W,3] u8; sems: dev [ncam,H,W] u8;  T: 4x4 row-major f64 (T_ego_world).
+ *     A point whose cam_idx lies outside [0, ncam) is dropped silently, whatever its u, v (the reference never looks at
+ *     them).  A point assigned to a camera whose u, v do not satisfy 1 < u < W - 1, 1 < v < H - 1 (on a bound, outside, NaN,
+ *     +-inf, -0.0) raises PCA_STATUS_UV_OUT_OF_IMAGE and is DROPPED: the call stores exactly the rows it would store without
+ *     that point, in both forms and both sample modes (the reference raises and stores nothing; the drop-in classes turn the
+ *     bit into that AssertionError).  On PCA_STATUS_STORE_OVERFLOW the rows below store.capacity are the right ones,
+ *     nothing at or behind it is written, and frame_off still counts every row the frame keeps: frame_off[slot + 1] =
+ *     frame_off[slot] + kept, which may lie behind capacity.
  * ------------------------------------------------------------------------------------------------ */
 int pca_nusc_sample_filter_transform(pca_ctx *ctx, const double *pc, const int64_t *cam_idx, int32_t n,
                                      const uint8_t *imgs, const uint8_t *sems, int ncam, int H, int W,
@@ -150,7 +157,9 @@ int pca_nusc_sample_filter_transform_batch(pca_ctx *ctx, const pca_nusc_frame *f
 
 /* pts_feat_from_img(pts_uv, img, method='bilinear') of the reference for a 2-D feature map (its bilinear branch only
  * works for those): datasets/nuscenes_utils.py:181-210, the arithmetic to the letter.  map: dev [H,W] f64; uv: dev [n,2]
- * f64 (u along x); out: dev [n] f64.  Raises PCA_STATUS_UV_OUT_OF_IMAGE where the reference's assert fails. */
+ * f64 (u along x); out: dev [n] f64.  Raises PCA_STATUS_UV_OUT_OF_IMAGE where the reference's assert fails: that point's out
+ * is 0.0, every other point's is what it is without it.  An integer u or v gives NaN (the reference's 0 / 0).  n = 0 returns
+ * 0 and writes nothing. */
 int pca_sample_bilinear(pca_ctx *ctx, const double *map /*dev*/, int H, int W, const double *uv /*dev*/, int32_t n,
                         double *out /*dev*/, void *stream);
 
@@ -160,6 +169,12 @@ int pca_sample_bilinear(pca_ctx *ctx, const double *map /*dev*/, int H, int W, c
  *     datasets/nuscenes_utils.py:46-60, :112-136 (view_points = nuscenes-devkit, restated).
  *     pc_lidar dev [n,3] f64.  T_cam_from_glob [ncam,16], K [ncam,9], wh [ncam,2] host arrays.
  *     Outputs dev: pc_in_ego [n,3], uv [n,2] f64, cam_idx [n] int64.
+ *     ncam: 0 .. 8, anything else returns -1 and writes nothing; ncam = 0 writes pc_in_ego, uv = 0 and cam_idx = -1.
+ *     n <= 0 returns 0 and writes nothing.  A point is taken by camera j where cz > 1e-3, 1 < u < w_j - 1 and
+ *     1 < v < h_j - 1, all strict; a point no camera takes (NaN and inf coordinates among them) keeps uv = 0, cam_idx = -1.
+ *     Every output is bit-equal to the reference's but for the sign of a NaN the arithmetic itself produced (0 x inf,
+ *     inf - inf in pc_in_ego of a point with an infinite coordinate): gfx950 clears it, x86 sets it.  The same holds for the
+ *     0 / 0 of pca_sample_bilinear at an integer coordinate.  Such values never reach the store.
  * ------------------------------------------------------------------------------------------------ */
 int pca_nusc_project_cams(pca_ctx *ctx, const double *pc_lidar, int32_t n, const double T_ego_from_lidar[16],
                           const double T_glob_from_ego[16], const double *T_cam_from_glob, const double *K,

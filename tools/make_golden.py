@@ -1472,6 +1472,89 @@ def case_lanes(ref, out_dir):
           [len(s) for s in survivors], os.path.getsize(path), 'bytes')
 
 
+def save_npz_reproducible(path, out):
+    """np.savez_compressed with a fixed member date and order, so that a second run writes the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for key in sorted(out):
+            info = zipfile.ZipInfo(key + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, 'w', force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(out[key]), allow_pickle=False)
+
+
+def case_nusc_front_edges(ref, out_dir):
+    """The NuScenes front end at its edges (tests/nusc_front_edges_common.py): homo_transform, NuScenesCamera.project_pts3d and
+    the camera loop, shaped as case_utils restates it, on every K0n scene -- per rig the indices the search chose, pc_in_ego, uv,
+    cam_idx, every camera's own mask and per family the largest distance from its bound in ulps, beside the rig's matrices;
+    pts_feat_from_img 'nearest' on image and class map camera by camera and homo_transform on every K1n scene without an
+    offender -- the stored rows (who goes to which camera and who is dropped is this file's own numpy); pts_feat_from_img 'bilinear' on a 2-D map at the sampler's coordinates, integer ones included."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import nusc_front_edges_common as ec
+    nu = ref.nu
+    out = {}
+    for name in ec.RIGS:
+        sel = ec.select(name)
+        sc = ec.k0n_scene(name, sel)
+        r, pc = sc['rig'], sc['pc']
+        n, ncam = pc.shape[0], len(r['wh'])
+        with np.errstate(all='ignore'):
+            pc_in_ego = nu.homo_transform(r['ego_from_lidar'], pc)
+            pc_in_glob = nu.homo_transform(r['glob_from_ego'], pc_in_ego)
+            pc_uv = np.zeros((n, 2))
+            pc_cam_idx = -np.ones(n, dtype=int)
+            masks = np.zeros((ncam, n), bool)
+            ulps = np.zeros(ncam * len(ec.BOUNDS))
+            for j in range(ncam):
+                cam = nu.NuScenesCamera.__new__(nu.NuScenesCamera)
+                cam.img_wh, cam.cam_K = r['wh'][j].copy(), r['K'][j].copy()
+                assert np.array_equal(np.linalg.inv(r['glob_from_cam'][j]), r['cam_from_glob'][j])     # (what the fixture keeps)
+                pc_in_cam = nu.homo_transform(np.linalg.inv(r['glob_from_cam'][j]), pc_in_glob)
+                uvj, m = cam.project_pts3d(pc_in_cam)
+                pc_uv[m] = uvj[m]
+                pc_cam_idx[m] = j
+                masks[j] = m
+                for b, bound in enumerate(ec.BOUNDS):
+                    s = sc['sections']['fam_%d_%s' % (j, bound)]
+                    val, inside = ec.bound_side(r, j, bound, uvj[s], pc_in_cam[s, 2])
+                    assert np.array_equal(inside, m[s]), (name, j, bound)      # nothing but this bound decides a family's points
+                    bv = ec.bound_value(r, j, bound)
+                    ulps[j * len(ec.BOUNDS) + b] = np.max(np.abs(val - bv)) / np.spacing(bv)
+        p = 'k0n_%s_' % name
+        for key in ('fam_idx', 'ovl_idx') + ec.RIG_KEYS:
+            out[p + key] = sel[key]
+        out[p + 'pc_in_ego'], out[p + 'uv'], out[p + 'cam_idx'] = pc_in_ego, pc_uv, pc_cam_idx.astype(np.int8)
+        out[p + 'masks'] = np.packbits(masks, axis=1)
+        out[p + 'fam_ulps'] = ulps
+        print('nusc_front_edges k0n', name, n, 'points,', int((pc_cam_idx >= 0).sum()), 'assigned; largest distance per family (ulps): %.3g .. %.3g'
+              % (ulps.min(), ulps.max()))
+    for name in ec.K1N_STACKS:
+        sc = ec.k1n_scene(name)
+        imgs, sems = ec.stack(name)
+        pc, cam = sc['pc'], sc['cam']
+        # the reference's own sampler per camera, on that camera's colour and class planes side by side; which points go to
+        # which camera, what is dropped and in what order the rest stays are written here in the project's words
+        feat = np.full((pc.shape[0], 4), -1.0)
+        for c in range(imgs.shape[0]):
+            of_c = np.flatnonzero(cam == c)
+            feat[of_c] = nu.pts_feat_from_img(pc[of_c, 4:6], np.dstack([imgs[c], sems[c]]), 'nearest')
+        keep = np.flatnonzero((feat >= 0).all(axis=1) & ~np.isin(feat[:, 3], sc['filters']))
+        rows = np.zeros((len(keep), 10))
+        rows[:, :3] = nu.homo_transform(sc['T'], pc[keep, :3])
+        rows[:, 3], rows[:, 4:8], rows[:, 8] = pc[keep, 3], feat[keep], pc[keep, 6]
+        p = 'k1n_%s_' % name
+        out[p + 'pc'], out[p + 'cam_idx'], out[p + 'filters'], out[p + 'T'], out[p + 'rows'] = pc, cam, np.array(sc['filters']), sc['T'], rows
+        out[p + 'kept'] = keep.astype(np.int32)
+        print('nusc_front_edges k1n', name, pc.shape[0], 'points,', rows.shape[0], 'stored, filters', sc['filters'])
+    fmap, uv = ec.bilinear_scene()
+    with np.errstate(all='ignore'):
+        out['bil_map'], out['bil_uv'], out['bil_out'] = fmap, uv, nu.pts_feat_from_img(uv, fmap, 'bilinear')
+    path = os.path.join(out_dir, 'nusc_front_edges.npz')
+    save_npz_reproducible(path, out)
+    assert os.path.getsize(path) < 1000 * 1000, os.path.getsize(path)
+    print('nusc_front_edges written:', os.path.getsize(path), 'bytes;', int(np.isnan(out['bil_out']).sum()), 'NaN of', len(uv), 'bilinear samples')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(
@@ -1486,7 +1569,7 @@ def main():
                  bev_edges=case_bev_edges, k1_edges=case_k1_edges, nusc=case_nusc,
                  utils=case_utils, sweeps=case_sweeps, sem_planes=case_sem_planes,
                  sweeps_edges=case_sweeps_edges, elev_partition=case_elev_partition,
-                 lanes=case_lanes)
+                 lanes=case_lanes, nusc_front_edges=case_nusc_front_edges)
     for name, fn in cases.items():
         if args.only and name not in args.only.split(','):
             continue
