@@ -18,14 +18,14 @@
 //     bev_tile_cells_heavy  the queued tiles, drawn by one resident 1024-thread workgroup per CU: 256-bin histograms
 //                       of 32 cells at a time filled straight from the record stream (two passes, no sort).
 // 'full' = present (+) future is formed per cell (counts add, min of mins, median of the union).
+// The view test and cell function, the owed re-transform chain and the counter tables' order are pca_bev_view.h's: one copy,
+// shared with the class planes and the elevation partition.
 #include "pca_bev_common.h"
+#include "pca_bev_view.h"
 #include "pca_k1_body.h"
 #include <cstdlib>
 #include <mutex>
 
-#define KEY_INVALID 0xffffffffu
-#define TS 8                      // tile side [cells]
-#define TCELLS (TS * TS)
 #define NFK (2 * TCELLS)          // fine keys per tile: cell_in_tile*2 + set
 #ifndef AB_THREADS
 #define AB_THREADS 1024           // workgroup size of the hist / scatter kernels
@@ -73,12 +73,9 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
     int slot_begin, slot_split, slot_end;
     int64_t max_points;
     pca_bev_params prm;
-    int n_pend;           // owed re-transforms, oldest first: transform k is owed by slots [slot_begin, pend_slot_end[k])
-    int write_back;       // apply them to the store (else to this raster only: they stay owed)
-    int pend_slot_end[PCA_BEV_MAX_CHAIN];   // ascending
-    Mat34 pend_T[PCA_BEV_MAX_CHAIN];
+    BevOwed owed;         // owed re-transforms, and whether this raster writes them back (pca_bev_view.h)
     int tx, T, G;
-    int Gr, Gp;           // counter tables: row length (>= G) and workgroups per XCD column block (table_pos)
+    int Gr, Gp;           // counter tables: row length (>= G) and workgroups per XCD column block (bev_table_pos)
     int tile_mult;        // bev_tile_cells: workgroup -> tile permutation (coprime to its period: T / 4 or T)
     int heavy_min;        // tiles with more records than this are bev_tile_cells_heavy's (<= RGB_CAP)
     int stagger;          // bev_tile_cells: start offset between the workgroups that share a CU, in units of s_sleep(16) (PCA_BEV_STAGGER)
@@ -115,15 +112,6 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
 
 struct Window { int64_t lo, hi, sp, c_lo, c_hi; };
 
-// Workgroup b of level 1 takes chunk b.  (Other orders were measured, the result does not depend on it -- segments, counters
-// and offsets are indexed by the chunk: the chunks around the present frame first -- the ones with points inside the view,
-// the expensive ones -- and outwards from there: 62.9 us against 61.0; a golden-ratio permutation that mixes expensive and
-// cheap chunks: 67.3 us.  Neighbouring chunks running at the same time is worth more than an even tail.)
-__device__ __forceinline__ int chunk_index(const BevArgs &a, int64_t lo, int64_t sp, int64_t chunk)
-{
-    (void)a; (void)lo; (void)sp; (void)chunk;
-    return (int)blockIdx.x;
-}
 #define K1_SEG 4096               // record slots of a K1 piece (one 1024 x 4 tile of k1_body keeps at most that many points)
 #define K1_RIDE 32                // K1 tiles that may ride in a level-1 launch (frames of up to 131 072 points): they come ON TOP of
                                   // the window's G pieces, so the counter tables and the record buffer are sized for G + K1_RIDE
@@ -144,7 +132,7 @@ __device__ __forceinline__ Window chunk_of(const BevArgs &a, int &g)
     w.hi = (hi0 - w.lo > a.max_points) ? w.lo + a.max_points : hi0;
     const int G = a.G - a.Gk;                               // chunks of the store's part of the window
     const int64_t chunk = (w.hi - w.lo + G - 1) / G;
-    g = chunk_index(a, w.lo, w.sp, chunk);                  // the piece: K1's tiles come first
+    g = (int)blockIdx.x;                                    // the piece: K1's tiles come first (other orders: docs/history.md)
     const int c = g - a.Gk;
     w.c_lo = w.lo + (int64_t)c * chunk;
     w.c_hi = w.c_lo + chunk < w.hi ? w.c_lo + chunk : w.hi;
@@ -152,23 +140,12 @@ __device__ __forceinline__ Window chunk_of(const BevArgs &a, int &g)
     return w;
 }
 __host__ __device__ __forceinline__ int64_t seg_stride(int64_t n, int G) { return (n + G - 1) / G; }
-// The per-(tile, workgroup) counter tables bh / boff are [tile][Gr] with workgroup g at position (g mod 8) Gp + g / 8:
-// workgroups are dealt to the eight XCDs round-robin, so the entries that share a cache line are written by workgroups of
-// ONE XCD -- the 32 of a round fill a whole 128-byte line in that XCD's L2, which then leaves it as one full-line write.
-// In plain [tile][g] order a line held the 4-byte stores of eight different L2s: 1 M partial-line writes per call, 100 MB
-// of write traffic for 75 MB of payload.  Level 2 reads a tile's row as one range either way.  Gp = 0: plain order.
+// (the order of the per-(tile, workgroup) counter tables bh / boff: bev_table_pos of pca_bev_view.h)
 // Are the pieces of THIS call ordered by half of the tile (a.split: 1 = if the window stays on level 1's register path -- the
 // host only knows an upper bound of the window, the kernels read its size --, 2 = always)?  The same answer in every kernel.
 __device__ __forceinline__ bool bev_split(const BevArgs &a, int64_t window_points)
 {
     return a.split == 2 || (a.split == 1 && window_points <= (int64_t)(a.G - a.Gk) * BIN_REG_P * AB_THREADS);
-}
-__device__ __forceinline__ int table_pos(const BevArgs &a, int g) { return a.Gp ? (g & 7) * a.Gp + (g >> 3) : g; }
-__device__ __forceinline__ int table_group(const BevArgs &a, int p)
-{
-    if (!a.Gp) return p;
-    const int x = p / a.Gp;
-    return (p - x * a.Gp) * 8 + x;                          // may be >= G: an unused place of the row
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -185,65 +162,14 @@ __device__ __forceinline__ int table_group(const BevArgs &a, int p)
 // ---------------------------------------------------------------------------------------------
 // One point of pass A: owed re-transform (returns the stored coordinates), BEV-frame key.  KEY_INVALID = not in the view.
 struct BinPoint { double x, y, z; uint32_t key; };
-struct PendHi { int64_t v[PCA_BEV_MAX_CHAIN]; };           // first point index that does NOT owe transform k
-// the owed re-transforms of point p, oldest first, each a separate fma chain (the roundings of one K2 pass per
-// transform); returns whether the point owed any
-__device__ __forceinline__ bool apply_owed(const BevArgs &a, const PendHi &pend_hi, int64_t p, double &X, double &Y, double &Z)
-{
-    bool moved = false;
-#pragma unroll 1                                            // (not unrolled: the coefficients are fetched when their turn
-    for (int k = 0; k < a.n_pend; ++k) {                    //  comes -- unrolled, all 48 are preloaded into scalar registers
-        const int64_t hi = k == 0 ? pend_hi.v[0] : k == 1 ? pend_hi.v[1] : k == 2 ? pend_hi.v[2] : pend_hi.v[3];   // and spill)
-        if (p < hi) {
-            const Mat34 &T = a.pend_T[k];
-            const double nx = row4(T.m + 0, X, Y, Z), ny = row4(T.m + 4, X, Y, Z), nz = row4(T.m + 8, X, Y, Z);
-            X = nx; Y = ny; Z = nz;
-            moved = true;
-        }
-    }
-    return moved;
-}
-// BEV-frame key of one point (stored coordinates X, Y, Z after the owed transforms): KEY_INVALID = not in the view
-__device__ __forceinline__ uint32_t view_key(const BevArgs &a, const Window &w, int64_t p, double X, double Y, double Z, uint8_t D)
-{
-    const pca_bev_params &q = a.prm;
-    const double v = q.view, vlo = -0.5 * v, vhi = 0.5 * v, pxd = (double)q.px, half_px = 0.5 * pxd;
-    const bool use_h = !(q.height_filter != q.height_filter);
-    const double x = X - q.origin[0];
-    const double y = Y - q.origin[1];
-    const double z = Z - q.origin[2];
-    double ax = q.R[0] * x; ax = fma(q.R[1], y, ax); ax = fma(q.R[2], z, ax);
-    double ay = q.R[3] * x; ay = fma(q.R[4], y, ay); ay = fma(q.R[5], z, ay);
-    double az = q.R[6] * x; az = fma(q.R[7], y, az); az = fma(q.R[8], z, az);
-    ax += q.dx;
-    ay += q.dy;
-    bool keep = (ax > vlo) && (ax < vhi) && (ay > vlo) && (ay < vhi);
-    if (use_h) keep = keep && (az < q.height_filter);
-    keep = keep && (D != 1);
-    uint32_t key = KEY_INVALID;
-    if (keep) {
-        int i = (int)floor(ax / v * pxd + half_px);
-        int j = (int)floor(ay / v * pxd + half_px);
-        i = i > q.px - 1 ? q.px - 1 : (i < 0 ? 0 : i);
-        j = j > q.px - 1 ? q.px - 1 : (j < 0 ? 0 : j);
-        const int row = q.px - 1 - j, col = i;
-        const uint32_t tile = (uint32_t)((row / TS) * a.tx + (col / TS));
-        const uint32_t fk = (uint32_t)(((row % TS) * TS + (col % TS)) * 2) + (p >= w.sp ? 1u : 0u);
-        key = (tile << 7) | fk;
-    }
-    return key;
-}
 // One point of pass A (memory path): owed re-transform (returns the stored coordinates), BEV-frame key.
-struct ViewConst;
-template <bool BAND = false>
-__device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, double Y, double Z, bool live, uint32_t set);
 template <bool BAND>
 __device__ __forceinline__ BinPoint bin_point(const BevArgs &a, const ViewConst &vc, const Window &w, const PendHi &pend_hi, int64_t p,
                                               double X, double Y, double Z, uint8_t D)
 {
     BinPoint r;
-    const bool moved = apply_owed(a, pend_hi, p, X, Y, Z);
-    if (moved && a.write_back) { a.st.x[p] = X; a.st.y[p] = Y; a.st.z[p] = Z; }
+    const bool moved = apply_owed(a.owed, pend_hi, p, X, Y, Z);
+    if (moved && a.owed.write_back) { a.st.x[p] = X; a.st.y[p] = Y; a.st.z[p] = Z; }
     r.x = X; r.y = Y; r.z = Z;
     r.key = view_key_lean<BAND>(vc, X, Y, Z, D != 1, p >= w.sp ? 1u : 0u);
     return r;
@@ -275,63 +201,6 @@ __device__ __forceinline__ void bin_store(const BevArgs &a, const uint32_t *dynb
     }
 }
 
-// The view test and cell key of pass A's register path, written for instruction count (the pass is bound by vector
-// issue, not by memory: ~270 instructions per point before, a third of them v_readlane of spilled scalars).  Same values
-// as view_key: R is a rotation about z (checked by the host), so R[2] z, R[5] z, R[6] x and R[7] y are exact zeros and
-// R[8] z is z -- for FINITE z; a point whose z is not finite is dropped here, as the reference drops it (0 * inf = NaN
-// poisons its x and y).
-struct ViewConst { double ox, oy, oz, r0, r1, r3, r4, dx, dy, vlo, vhi, v, rv, pxd, half_px, hf; int px, tx; bool use_h; uint32_t br0, brows; };
-__device__ __forceinline__ ViewConst view_const(const BevArgs &a)
-{
-    const pca_bev_params &q = a.prm;
-    ViewConst c;
-    c.ox = q.origin[0]; c.oy = q.origin[1]; c.oz = q.origin[2];
-    c.r0 = q.R[0]; c.r1 = q.R[1]; c.r3 = q.R[3]; c.r4 = q.R[4];
-    c.dx = q.dx; c.dy = q.dy;
-    c.v = q.view; c.rv = 1.0 / q.view; c.vlo = -0.5 * q.view; c.vhi = 0.5 * q.view; c.pxd = (double)q.px; c.half_px = 0.5 * c.pxd;
-    // (handing 1 / view, (double)px and px / 2 over from the host instead was measured: 57.7-57.8 us against 56.8-57.2)
-    c.hf = q.height_filter; c.use_h = !(q.height_filter != q.height_filter);
-    c.px = q.px; c.tx = a.tx;
-    c.br0 = (uint32_t)a.band_r0; c.brows = (uint32_t)a.band_rows;   // (read by the BAND variant only)
-    return c;
-}
-// BAND (banded rasters, px > 1024): i, j, the clamp and the row are those of the FULL grid; a point whose tile row lies outside
-// the band [br0, br0 + brows) gets KEY_INVALID, the others the key of their tile numbered within the band.
-template <bool BAND>
-__device__ __forceinline__ uint32_t view_key_lean(const ViewConst &c, double X, double Y, double Z, bool live, uint32_t set)
-{
-    const double x = X - c.ox, y = Y - c.oy;
-    const double ax = fma(c.r1, y, c.r0 * x) + c.dx;
-    const double ay = fma(c.r4, y, c.r3 * x) + c.dy;
-    bool keep = live && (ax > c.vlo) && (ax < c.vhi) && (ay > c.vlo) && (ay < c.vhi) && (fabs(Z) < __builtin_huge_val());
-    if (c.use_h) keep = keep && (Z - c.oz < c.hf);
-    uint32_t key = KEY_INVALID;
-    if (keep) {
-        // floor(a / view * px + px / 2), the reference's expression.  The IEEE division (~22 instructions) is replaced by
-        // the quotient estimate  q = a rv,  q += fma(-q, view, a) rv  (within one ulp of the rounded quotient): the floor
-        // can only differ if the sum lands within a few ulps of an integer, and a sum within 1e-9 of one is recomputed
-        // with the real division (about two points in a billion).  The margin holds up to the largest grid, px = 4096: |q| < 1/2,
-        // so ulp(q) px <= 2^-53 * 4096 ~ 4.5e-13, far below 1e-9.
-        const double qx0 = ax * c.rv, qy0 = ay * c.rv;
-        const double qx = fma(fma(-qx0, c.v, ax), c.rv, qx0), qy = fma(fma(-qy0, c.v, ay), c.rv, qy0);
-        double tx = qx * c.pxd + c.half_px, ty = qy * c.pxd + c.half_px;
-        double fx = floor(tx), fy = floor(ty);
-        if ((tx - fx < 1e-9) | (fx + 1.0 - tx < 1e-9) | (ty - fy < 1e-9) | (fy + 1.0 - ty < 1e-9)) {
-            fx = floor(ax / c.v * c.pxd + c.half_px);
-            fy = floor(ay / c.v * c.pxd + c.half_px);
-        }
-        int i = (int)fx;
-        int j = (int)fy;
-        i = i > c.px - 1 ? c.px - 1 : (i < 0 ? 0 : i);
-        j = j > c.px - 1 ? c.px - 1 : (j < 0 ? 0 : j);
-        const uint32_t row = (uint32_t)(c.px - 1 - j), col = (uint32_t)i;
-        const uint32_t trow = BAND ? row / TS - c.br0 : row / TS;   // (BAND: wraps to a large number above the band)
-        const uint32_t tile = trow * (uint32_t)c.tx + (col / TS);
-        if (!BAND || trow < c.brows) key = (tile << 7) | ((((row % TS) * TS + (col % TS)) * 2u) + set);
-    }
-    return key;
-}
-
 // The first REG_P * 1024 points of a chunk stay in REGISTERS between the passes (key and stored z; colour and intensity of
 // the kept points are gathered at the start of pass B, all of a lane's gathers back to back), so pass B is LDS cursors and
 // 16-byte stores.  A 200-frame KITTI window is ~10 000 points per chunk: all of it.  Whatever a chunk holds beyond that
@@ -345,7 +214,7 @@ __device__ __forceinline__ void bin_scan_tables(const BevArgs &a, const uint32_t
 {
     const int per = (a.T + AB_THREADS - 1) / AB_THREADS;
     const int t0 = threadIdx.x * per;
-    const int gp = table_pos(a, g);
+    const int gp = bev_table_pos(a.Gp, g);
     uint32_t sum = 0;
     if (split) { for (int k = 0; k < per; ++k) sum += t0 + k < a.T ? s_h[2 * (t0 + k)] + s_h[2 * (t0 + k) + 1] : 0u; }
     else { for (int k = 0; k < per; ++k) sum += t0 + k < a.T ? s_h[t0 + k] : 0u; }
@@ -415,10 +284,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     }
     for (int t = threadIdx.x; t < n_hist; t += AB_THREADS) s_h[t] = 0;
     __syncthreads();
-    PendHi pend_hi;
-#pragma unroll
-    for (int k = 0; k < PCA_BEV_MAX_CHAIN; ++k)
-        pend_hi.v[k] = (k < a.n_pend && a.pend_slot_end[k] > a.slot_begin) ? a.frame_off[a.pend_slot_end[k]] : w.lo;
+    const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, w.lo);
     const int64_t reg_hi = w.c_lo + (int64_t)REG_P * AB_THREADS < w.c_hi ? w.c_lo + (int64_t)REG_P * AB_THREADS : w.c_hi;
     // ---- pass A, register part ----
     // Every load is issued by every lane, in straight-line code: a lane past the end of the chunk reads the chunk's first
@@ -438,7 +304,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     if (REG_P > 0 && n_reg > 0) {
         const double *xb = a.st.x + w.c_lo, *yb = a.st.y + w.c_lo, *zb = a.st.z + w.c_lo;
         const uint8_t *db = a.st.dyn + w.c_lo;
-        const ViewConst vc = view_const(a);
+        const ViewConst vc = view_const(a.prm, a.tx, a.band_r0, a.band_rows);
         // (Issuing the loads of batch b + 1 before batch b is worked on -- two register sets -- was tried twice: with batches
         // of four 128 VGPRs and spills, 6 us slower; with batches of 2 / 3 / 4 and no spills 62.1 / 62.0 / 63.1 against 60.6 us:
         // the pass does not wait for its point loads.  So was dealing the window to the workgroups in round-robin blocks of 1024 points instead of
@@ -456,14 +322,15 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
             }
         };
         auto work = [&](int j0, double (&X)[UNR], double (&Y)[UNR], double (&Z)[UNR], uint32_t (&D)[UNR]) {
-            // the owed re-transforms, oldest first, each a separate fma chain (the roundings of one K2 pass per transform).
+            // the owed re-transforms, oldest first, each a separate fma chain (the roundings of one K2 pass per transform):
+            // the same chain as apply_owed of pca_bev_view.h, in a form tuned for this path (docs/history.md, "BEV level 1, round 3").
             // Transform k's twelve coefficients are fetched (scalar loads) when its turn comes instead of all forty-eight
             // living in scalar registers through the whole pass; applied branch-free: all but the newest frames' points
             // owe every pending transform, and UNR independent chains interleave.
             uint32_t n_moved = 0;                           // lanes i < n_moved were moved by some transform
 #pragma unroll 1
-            for (int k = 0; k < a.n_pend; ++k) {
-                const Mat34 &Tk = a.pend_T[k];
+            for (int k = 0; k < a.owed.n_pend; ++k) {
+                const Mat34 &Tk = a.owed.pend_T[k];
                 const uint32_t n_owe = rel(k == 0 ? pend_hi.v[0] : k == 1 ? pend_hi.v[1] : k == 2 ? pend_hi.v[2] : pend_hi.v[3]);
                 if (n_owe == 0) continue;                   // (uniform)
                 n_moved = n_owe > n_moved ? n_owe : n_moved;
@@ -492,7 +359,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
                     }
                 }
             }
-            if (a.write_back && n_moved > 0) {
+            if (a.owed.write_back && n_moved > 0) {
                 double *xw = a.st.x + w.c_lo, *yw = a.st.y + w.c_lo, *zw = a.st.z + w.c_lo;
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
@@ -520,7 +387,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     BIN_STAMP(1);
     // ---- pass A, memory part (what the chunk holds beyond the registers) ----
     constexpr int MUNR = BIN_UNR;
-    const ViewConst vcm = view_const(a);
+    const ViewConst vcm = view_const(a.prm, a.tx, a.band_r0, a.band_rows);
     for (int64_t base = reg_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
         double X[MUNR], Y[MUNR], Z[MUNR];
         uint8_t D[MUNR];
@@ -583,7 +450,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
         }
     }
     BIN_STAMP(4);
-    const bool stale = a.n_pend > 0 && !a.write_back;
+    const bool stale = a.owed.n_pend > 0 && !a.owed.write_back;
     for (int64_t base = reg_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
         uint32_t key[MUNR], pos[MUNR], rgbs[MUNR];
         double zz[MUNR], iv[MUNR], xs[MUNR], ys[MUNR];
@@ -609,7 +476,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
         for (int u = 0; u < MUNR; ++u) {
             const int64_t p = base + u * AB_THREADS;
             const bool ok = key[u] != KEY_INVALID;
-            if (ok && stale) apply_owed(a, pend_hi, p, xs[u], ys[u], zz[u]);
+            if (ok && stale) apply_owed(a.owed, pend_hi, p, xs[u], ys[u], zz[u]);
             pos[u] = ok ? seg + atomicAdd(&s_cur[key[u] >> hs], 1u) : 0u;
         }
 #pragma unroll
@@ -617,7 +484,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
             if (key[u] != KEY_INVALID) bin_store<I64>(a, s_dyn, pos[u], key[u], rgbs[u], zz[u], iv[u], (float)iv[u]);
     }
     BIN_STAMP(5);
-    if ((a.dbg & 32) && threadIdx.x == 0 && blockIdx.x < 1024) { g_dbg_stamps[blockIdx.x][6] = (unsigned long long)a.n_pend * 2 + a.write_back; g_dbg_stamps[blockIdx.x][7] = __smid(); }
+    if ((a.dbg & 32) && threadIdx.x == 0 && blockIdx.x < 1024) { g_dbg_stamps[blockIdx.x][6] = (unsigned long long)a.owed.n_pend * 2 + a.owed.write_back; g_dbg_stamps[blockIdx.x][7] = __smid(); }
 }
 
 // A tile's records lie in up to G pieces, one per level-1 workgroup.  RecMap (LDS) turns the tile-local record number
@@ -633,7 +500,7 @@ struct RecMap {
 // out as [first half][second half] and left the first half's count in bh0.
 __device__ __forceinline__ uint32_t recmap_build(RecMap &M, const BevArgs &a, int tile, int nthreads, uint16_t *owner = nullptr, int half = -1)
 {
-    // (places of the row, not workgroups: see table_pos; a place beyond the last workgroup counts as an empty piece)
+    // (places of the row, not workgroups: see bev_table_pos; a place beyond the last workgroup counts as an empty piece)
     const int per = (a.Gr + nthreads - 1) / nthreads;
     const int g0 = threadIdx.x * per;
     const uint32_t *cnt = a.bh + (int64_t)tile * a.Gr, *off = a.boff + (int64_t)tile * a.Gr;
@@ -643,7 +510,7 @@ __device__ __forceinline__ uint32_t recmap_build(RecMap &M, const BevArgs &a, in
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (k < per && g0 + k < a.Gr) {
-            grp[k] = table_group(a, g0 + k);
+            grp[k] = bev_table_group(a.Gp, g0 + k);
             if (grp[k] < a.G) {
                 c[k] = cnt[g0 + k]; o[k] = off[g0 + k];
                 if (half >= 0) c0[k] = a.bh0[(int64_t)tile * a.Gr + g0 + k];     // (uniform; read before it is known to be valid: never used then)
@@ -1627,7 +1494,7 @@ struct BinK1Tail {
         }
         for (int t = threadIdx.x; t < n_hist; t += AB_THREADS) s_h[t] = 0;
         __syncthreads();
-        const ViewConst vc = view_const(a);
+        const ViewConst vc = view_const(a.prm, a.tx, a.band_r0, a.band_rows);
         const uint32_t set = a.k1_slot >= a.slot_split ? 1u : 0u;
         const int lane = threadIdx.x & 63;
         uint32_t rkey[PPT];
@@ -1837,17 +1704,9 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
                        void *workspace, int64_t workspace_bytes, double *planes, uint16_t *planes_f16,
                        double *extra_planes, BevArgs &a)
 {
-    if (n_pending < 0 || n_pending > PCA_BEV_MAX_CHAIN || (n_pending > 0 && (!pending_Ts || !pending_slot_ends))) {
-        ctx->err = "bev: bad chain of owed transforms";
-        return -1;
-    }
     if (!store || !frame_off || !prm || !workspace || (!planes && !planes_f16)) { ctx->err = "bev: bad arguments"; return -1; }
     PX_CHECK(ctx, prm->px);
-    // the elevation plane is min(z - origin_z): the rotation has to leave z alone (rotation_matrix_3d of the reference)
-    if (!(prm->R[6] == 0.0 && prm->R[7] == 0.0 && prm->R[8] == 1.0 && prm->R[2] == 0.0 && prm->R[5] == 0.0)) {
-        ctx->err = "bev: R must be a rotation about the z axis (R[2] = R[5] = R[6] = R[7] = 0, R[8] = 1)";
-        return -1;
-    }
+    if (bev_check_rotation(ctx, "bev", prm)) return -1;
     if (!(slot_begin <= slot_split && slot_split <= slot_end)) { ctx->err = "bev: need slot_begin <= slot_split <= slot_end"; return -1; }
     if (max_points >= (1ll << 32)) { ctx->err = "bev: window too large for 32-bit positions"; return -1; }
     const BevLayout l = bev_layout(max_points, prm->px);
@@ -1858,17 +1717,8 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     a.slot_begin = slot_begin; a.slot_split = slot_split; a.slot_end = slot_end;
     a.max_points = max_points;
     a.prm = *prm;
-    a.n_pend = n_pending;
-    a.write_back = write_back ? 1 : 0;
-    for (int k = 0; k < PCA_BEV_MAX_CHAIN; ++k) {
-        a.pend_slot_end[k] = slot_begin;
-        for (int i = 0; i < 12; ++i) a.pend_T[k].m[i] = 0.0;
-        if (k >= n_pending) continue;
-        if (pending_slot_ends[k] > slot_end) { ctx->err = "bev: a pending slot end lies beyond the window"; return -1; }
-        if (k > 0 && pending_slot_ends[k] < pending_slot_ends[k - 1]) { ctx->err = "bev: pending slot ends must ascend"; return -1; }
-        a.pend_slot_end[k] = pending_slot_ends[k];
-        for (int i = 0; i < 12; ++i) a.pend_T[k].m[i] = pending_Ts[16 * k + i];
-    }
+    if (bev_fill_owed(ctx, "bev", pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, a.owed)) return -1;
+    a.owed.write_back = write_back ? 1 : 0;
     a.tx = tiles_x(prm->px);
     a.band_rows = band_rows(prm->px);                       // (< tx: a banded raster, bev_set_band picks the band)
     a.band_r0 = 0;
@@ -1961,7 +1811,7 @@ static int bev_decide_k1_ride(pca_ctx *ctx, const BevArgs &a, bool tuned, size_t
     const int fk = (int)PCA_ENV_ONCE("PCA_FUSE_K1", 1);
     const pca_ctx::K1Pending &pd = ctx->k1_pend;
     bool owed_ok = true;                                    // (a transform owed by the riding frame itself: its end is not written yet)
-    for (int k = 0; k < a.n_pend; ++k) owed_ok = owed_ok && a.pend_slot_end[k] <= pd.slot;
+    for (int k = 0; k < a.owed.n_pend; ++k) owed_ok = owed_ok && a.owed.pend_slot_end[k] <= pd.slot;
     const bool fuse = fk && owed_ok && !a.intensity64 && pd.stream == s && pd.slot == a.slot_end - 1 && pd.slot >= a.slot_begin &&
                       pd.frame_off == a.frame_off && pd.store.x == a.st.x && lds <= K1_RIDE_LDS && pd.fr.n <= K1_RIDE * K1_SEG &&
                       pd.fr.n <= a.max_points && pca_k1_prepare_pending(ctx, k1a, nt, s) == 0 && *nt <= K1_RIDE;
@@ -1984,7 +1834,7 @@ static int bev_decide_bin_range(pca_ctx *ctx, BevArgs &a, bool tuned, const BevB
     // piece per CU: a piece costs ~15 us before its first point, two rounds of half-size pieces take almost twice as long as
     // one (profiles/r05_experiments/bev_cull_frames_out_of_view.txt).  The count comes from the device through a host-visible
     // word and only sizes the launch: a window that turns out larger goes through the memory path as ever.
-    if (!r.given || !PCA_ENV_ONCE("PCA_BEV_CULL", 1) || (a.n_pend > 0 && a.write_back)) return 0;
+    if (!r.given || !PCA_ENV_ONCE("PCA_BEV_CULL", 1) || (a.owed.n_pend > 0 && a.owed.write_back)) return 0;
     const int f = r.first > a.slot_begin ? r.first : a.slot_begin, e = r.end < a.slot_end ? r.end : a.slot_end;
     a.bin_first = f; a.bin_end = e < f ? f : e;
     if (!tuned) return 0;
@@ -2067,7 +1917,7 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
     for (int r0 = 0, rows = a.band_rows; r0 < a.tx; r0 += rows) {
         if (!tuned) {
             bev_set_band(a, r0);
-            if (r0 > 0 && a.write_back) a.n_pend = 0;       // band 0 has stored them
+            if (r0 > 0 && a.owed.write_back) a.owed.n_pend = 0;       // band 0 has stored them
         }
         if (bev_launch_raster(ctx, ks, a, nt ? &k1a : nullptr, lds, s)) return -1;
     }

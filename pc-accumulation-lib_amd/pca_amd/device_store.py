@@ -53,10 +53,9 @@ class DeviceStore:
         self._ws = None
         self._ws_many = None
         self._ws_points, self._ws_px = 0, 0
-        self._ws_cls = None      # scratch of bev_class_planes, its own (a main raster may have sized _ws differently)
-        self._ws_cls_points, self._ws_cls_px = 0, 0
-        self._ws_elev = None     # scratch of bev_elev_partition, its own for the same reason
-        self._ws_elev_points, self._ws_elev_px = 0, 0
+        # scratch of bev_class_planes and of bev_elev_partition, each its own (a main raster may have sized _ws differently):
+        # name -> [buffer, the points it is sized for, px], see _side_workspace
+        self._ws_side = {}
         self._dedup_ws = None
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
@@ -597,6 +596,17 @@ class DeviceStore:
             self._pending = []
         self._k1_noted = None                      # (a raster takes a noted K1 along or runs it first: nothing is noted any more)
 
+    def _side_workspace(self, name, workspace_bytes, max_points, px):
+        """The scratch of a side pass (bev_class_planes, bev_elev_partition), fit for max_points at `px`."""
+        ws = self._ws_side.setdefault(name, [None, 0, 0])
+        if ws[0] is None or max_points > ws[1] or px != ws[2]:
+            # sized with headroom so that a window growing frame by frame does not reallocate every call
+            ws[1], ws[2] = int(max_points * 1.25) + 1, px
+        need = workspace_bytes(ws[1], px)              # (asked every call: PCA_BEV_CLASS_G / PCA_BEV_ELEV_G change it)
+        if ws[0] is None or ws[0].numel() < need:
+            ws[0] = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        return ws[0]
+
     def bev_class_planes(self, split_frame, prm, groups, first_frame=0, last_frame=None, want_counts=False):
         """Planes of any semantic class groups over live frames [first_frame, last_frame), 'present' = frames before
         split_frame (pca_bev_class_planes: one counts-only pass for all groups).  groups: a list of class-index lists (1..16
@@ -614,11 +624,7 @@ class DeviceStore:
         # the owed chain, read only (bev_pending flushes it when this raster does not cover what is owed)
         n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
         max_points = self.max_window_points()
-        if self._ws_cls is None or max_points > self._ws_cls_points or px != self._ws_cls_px:
-            self._ws_cls_points, self._ws_cls_px = int(max_points * 1.25) + 1, px
-            need = lib.pca_bev_class_workspace_bytes(self._ws_cls_points, px)
-            if self._ws_cls is None or self._ws_cls.numel() < need:
-                self._ws_cls = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        ws = self._side_workspace('class', lib.pca_bev_class_workspace_bytes, max_points, px)
         shape = (3, max(ng, 1), max(px, 1), max(px, 1))
         p16 = torch.empty(shape, dtype=torch.float16, device=self.device)
         p64 = torch.empty(shape, dtype=torch.float64, device=self.device)
@@ -626,7 +632,7 @@ class DeviceStore:
         st = self.c_store()
         ctx.check(lib.pca_bev_class_planes(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
                                            self.head + split_frame, self.head + last_frame, max_points, C.byref(prm), cg, ng,
-                                           pend_T, pend_ends, n_pend, self._ws_cls.data_ptr(), self._ws_cls.numel(),
+                                           pend_T, pend_ends, n_pend, ws.data_ptr(), ws.numel(),
                                            p64.data_ptr(), p16.data_ptr(), None if cnt is None else cnt.data_ptr(),
                                            ctx.stream()))
         return p16, p64, cnt
@@ -654,12 +660,7 @@ class DeviceStore:
         n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
         bound = self.max_window_points()
         max_points = bound if max_points is None else max(int(max_points), 1)
-        if self._ws_elev is None or max_points > self._ws_elev_points or px != self._ws_elev_px:
-            # sized with headroom so that a window growing frame by frame does not reallocate every call
-            self._ws_elev_points, self._ws_elev_px = int(max_points * 1.25) + 1, px
-        need = lib.pca_bev_elev_workspace_bytes(self._ws_elev_points, px)      # (asked every call: PCA_BEV_ELEV_G changes it)
-        if self._ws_elev is None or self._ws_elev.numel() < need:
-            self._ws_elev = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        ws = self._side_workspace('elev', lib.pca_bev_elev_workspace_bytes, max_points, px)
         side = max(px, 1)
         elev = torch.empty((side, side), dtype=torch.float64, device=self.device)
         obs = torch.empty((side, side), dtype=torch.uint8, device=self.device)
@@ -668,8 +669,8 @@ class DeviceStore:
         st = self.c_store()
         ctx.check(lib.pca_bev_elev_partition(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
                                              self.head + last_frame, max_points, C.byref(prm), float(elev_thresh),
-                                             1 if include_dyn else 0, pend_T, pend_ends, n_pend, self._ws_elev.data_ptr(),
-                                             self._ws_elev.numel(), elev.data_ptr(), obs.data_ptr(), flags.data_ptr(),
+                                             1 if include_dyn else 0, pend_T, pend_ends, n_pend, ws.data_ptr(),
+                                             ws.numel(), elev.data_ptr(), obs.data_ptr(), flags.data_ptr(),
                                              counts.data_ptr(), ctx.stream()))
         self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
         lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
