@@ -641,6 +641,13 @@ int pca_host_d2h_wait(pca_ctx *ctx, int ticket);
  *     everything enqueued on `stream` so far, and the return value is a ticket for pca_host_d2h_wait (or -1).  A
  *     pca_host_d2h_async issued after it copies the results behind the kernels.  src, the table, the outputs and the
  *     workspace are to be left alone until the ticket (or a later one) has been waited for.
+ * pca_deflate_chunks_dyn   the same call -- signature, workspace, ticket, stream and lifetime rules, outputs, bound -- with
+ *     an entropy coder chosen per chunk: the piece is the smaller of the fixed-Huffman piece pca_deflate_chunks makes and a
+ *     dynamic-Huffman piece (BTYPE 10) of the very same tokens, decided by exact bit count, a tie going to fixed; so no
+ *     piece is larger than pca_deflate_chunks makes it.  The block type of a piece is bits 1-2 of its first byte.  The
+ *     literal/length code is a Huffman code of the chunk's own token histogram limited to 15 bits (optimal whenever the
+ *     unlimited tree is no deeper), sent up to the highest used symbol; the distance code always is two one-bit codes
+ *     (distances 1 and 2); the code lengths go through one fixed, complete code-length code with its run symbols.
  * pca_host_crc32_combine   CRC-32 of A || B from crc(A), crc(B) and the length of B (GF(2) arithmetic, no data pass;
  *     zlib's crc32_combine, which Python's zlib module does not expose).  len_b < 0: returns 0.
  * pca_host_gzip_assemble   one gzip member from n_pieces pieces in order: the 10-byte header, the pieces, a final empty
@@ -659,6 +666,9 @@ int64_t pca_deflate_workspace_bytes(int64_t n_chunks);
 int pca_deflate_chunks(pca_ctx *ctx, const void *src /*dev*/, const pca_deflate_chunk *chunk_table /*dev*/, int64_t n_chunks,
                        void *out /*dev*/, uint32_t *out_sizes /*dev*/, uint32_t *out_crcs /*dev*/, void *workspace /*dev*/,
                        void *stream);
+int pca_deflate_chunks_dyn(pca_ctx *ctx, const void *src /*dev*/, const pca_deflate_chunk *chunk_table /*dev*/, int64_t n_chunks,
+                           void *out /*dev*/, uint32_t *out_sizes /*dev*/, uint32_t *out_crcs /*dev*/, void *workspace /*dev*/,
+                           void *stream);
 uint32_t pca_host_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
 int64_t pca_host_gzip_assemble(int32_t n_pieces, const void *const *piece, const int64_t *piece_bytes, const int64_t *raw_bytes,
                                const uint32_t *crc, void *out, int64_t out_cap);

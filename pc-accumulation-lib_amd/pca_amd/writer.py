@@ -6,7 +6,11 @@ codec='device' (opt-in; PCA_WRITER_CODEC=device for the shared writer) leaves th
 the pickle of a sample is laid out from zero-filled stand-ins, the 15 plane payloads are located in it, and those byte
 ranges of the device planes are compressed there (pca_deflate_chunks: fixed-Huffman pieces that concatenate bytewise).  The
 worker threads then only splice: pickle fragments from the host as stored blocks, device pieces as they are, one gzip
-member (pca_host_gzip_assemble).  The file inflates to exactly pickle.dumps(dict(bev))."""
+member (pca_host_gzip_assemble).  The file inflates to exactly pickle.dumps(dict(bev)).
+
+huffman='dynamic' (opt-in on top of the device codec; PCA_WRITER_HUFFMAN=dynamic for the shared writer) compresses with
+pca_deflate_chunks_dyn: the same tokens, each chunk with a Huffman code of its own where that is smaller.  Same pieces,
+same splice, smaller files."""
 import atexit
 import ctypes as C
 import gzip
@@ -137,7 +141,7 @@ class _DeviceJob:
     kernels, then ONE copy of (sizes, crcs, bytes).  The samples of a generate_bev_many share it.  Holds planes, table,
     outputs and workspace until the copy has been waited for."""
 
-    def __init__(self, planes):
+    def __init__(self, planes, huffman='fixed'):
         import weakref
 
         import torch
@@ -153,8 +157,8 @@ class _DeviceJob:
         dev = torch.empty(8 * n + k * lay.cap, dtype=torch.uint8, device=planes.device)
         self.host = torch.empty(8 * n + k * lay.cap, dtype=torch.uint8, pin_memory=True)
         p = dev.data_ptr()
-        rc = ctx.lib.pca_deflate_chunks(ctx.h, planes.data_ptr(), table.data_ptr(), n, p + 8 * n, p, p + 4 * n, ws.data_ptr(),
-                                        ctx.stream())
+        deflate = ctx.lib.pca_deflate_chunks_dyn if huffman == 'dynamic' else ctx.lib.pca_deflate_chunks
+        rc = deflate(ctx.h, planes.data_ptr(), table.data_ptr(), n, p + 8 * n, p, p + 4 * n, ws.data_ptr(), ctx.stream())
         if rc < 0:
             ctx.check(rc)
         # (rc is the ticket of the kernels alone, for callers that leave the pieces on the device.  The copy below runs behind
@@ -243,10 +247,13 @@ class _Item:
 
 class AsyncBevWriter:
 
-    def __init__(self, n_threads=4, compresslevel=9, max_pending=64, codec='host'):
+    def __init__(self, n_threads=4, compresslevel=9, max_pending=64, codec='host', huffman='fixed'):
         if codec not in ('host', 'device'):
             raise ValueError(f"codec must be 'host' or 'device', not {codec!r}")
+        if huffman not in ('fixed', 'dynamic'):
+            raise ValueError(f"huffman must be 'fixed' or 'dynamic', not {huffman!r}")
         self.codec = codec
+        self.huffman = huffman               # the device codec's entropy coder; the host codec does not look at it
         # device codec: samples written from device pieces / samples that came from the device but were written by the host
         # codec all the same (pickle without the expected byte strings, a LazyBev made before the codec was selected or
         # submitted a second time, plane arrays replaced after the sample filled in)
@@ -352,7 +359,8 @@ class AsyncBevWriter:
         job = self._jobs.get(id(planes))
         if job is None or job.planes_ref() is not planes:
             self._jobs = {k: j for k, j in self._jobs.items() if j.planes_ref() is not None}
-            job = self._jobs[id(planes)] = _DeviceJob(planes)
+            # (the default goes out as the one-argument call it has always been: wrappers of _DeviceJob take `planes` alone)
+            job = self._jobs[id(planes)] = _DeviceJob(planes, self.huffman) if self.huffman != 'fixed' else _DeviceJob(planes)
         return job
 
     def submit(self, bev, filename, write_dir):
@@ -444,7 +452,8 @@ def shared_writer():
     global _shared
     if _shared is None:
         _shared = AsyncBevWriter(n_threads=int(os.environ.get('PCA_WRITER_THREADS', '4')),
-                                 codec=os.environ.get('PCA_WRITER_CODEC', 'host'))
+                                 codec=os.environ.get('PCA_WRITER_CODEC', 'host'),
+                                 huffman=os.environ.get('PCA_WRITER_HUFFMAN', 'fixed'))
         atexit.register(_shared.close)
     return _shared
 
