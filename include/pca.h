@@ -674,6 +674,52 @@ int64_t pca_host_gzip_assemble(int32_t n_pieces, const void *const *piece, const
                                const uint32_t *crc, void *out, int64_t out_cap);
 
 /* ------------------------------------------------------------------------------------------------
+ * KP: the preview sheet of a BEV sample as a PNG made on the device.  Replaces, opt-in (PCA_VIZ=device, pca_amd/preview.py),
+ * the matplotlib figure the drivers save beside every sample (run_kitti360_bev_gen.py:267-270 of the reference calls
+ * viz_bev); the layout of the picture is this library's own.
+ *
+ * The sheet of one sample [21,px,px] f16 (set-major, 7 planes per set) is an RGB8 image 3 px high and 5 px wide: row block s
+ * = the set, column block c = the panel road, intensity, rgb, dynamic, elevation (planes 7 s + {0, 1, 2..4, 5, 6}); pixel
+ * (r, q) of a panel shows plane element [r][q].  A scalar panel maps v (f16 -> f32) to lut[clamp(floor((v - lo) * scale), 0,
+ * 255)] in f32 (NaN -> 0, +inf -> 255, -inf -> 0); the rgb panel to floor(min(max(v, 0), 1) * 255 + 0.5) per channel (NaN ->
+ * 0).  Polylines of a (sample, set) are drawn in (255, 0, 0), one pixel wide, over all five panels of that row block: grid
+ * point (x, y) is panel pixel column x, row px - 1 - y; a segment (x0, y0) -> (x1, y1) with n = max(|dx|, |dy|) covers, for
+ * s = 0 .. n, (x0 + floordiv(2 s dx + n, 2 n), y0 + floordiv(2 s dy + n, 2 n)) (the one point when n = 0); points outside
+ * the grid are skipped; a polyline of one vertex is one point.  Coordinates beyond +-2^29 are taken as +-2^29.
+ *
+ * pca_preview_stream_bytes   (1 + 15 px) * 3 px: the PNG scanline stream of one sheet (-1: px outside 1 .. 4096).
+ * pca_preview_sheets   planes: device [k,21,px,px] f16; verts: device [n_verts][2] int32 (x, y); polylines: device,
+ *     n_polylines records (an entry that names no sample, set or vertices of the call is skipped); lut: device [256][3] u8;
+ *     ranges: HOST [4][2] f32, (lo, scale) of road, intensity, dynamic, elevation, scale = 256 / (hi - lo); filter: the PNG
+ *     filter of every scanline, 0 None, 1 Sub (3 bytes per pixel), 2 Up.  Writes to out_stream (device, k *
+ *     pca_preview_stream_bytes(px), any alignment) the scanlines of every sheet, each one filter-type byte and 15 px
+ *     filtered bytes, overlay included; nothing else is written.  workspace: pca_preview_workspace_bytes(k, px), device.
+ * pca_adler32_chunks   out[c] (device) = Adler-32, from the initial value 1, of chunk c of chunk_table (device; lengths as
+ *     for pca_deflate_chunks) alone: zlib.adler32(chunk).  A zero-length chunk gives 1.
+ *     Both calls follow pca_deflate_chunks' stream and lifetime rules: the context's side stream, behind everything enqueued
+ *     on `stream`, the return value a ticket for pca_host_d2h_wait (or -1).
+ * pca_host_adler32_combine   Adler-32 of A || B from adler(A), adler(B) and the length of B (zlib's adler32_combine).
+ *     len_b < 0: returns 0.
+ * pca_host_png_assemble   one PNG: signature, IHDR (8 bits, colour type 2, no interlace), ONE IDAT holding the zlib header
+ *     78 01, the pieces in order (byte-aligned pieces of a DEFLATE stream without a final block, as pca_deflate_chunks makes
+ *     them of the chunks of a scanline stream), a final empty fixed block and `adler` (of the whole scanline stream), IEND;
+ *     chunk CRCs are computed here.  Returns the file's length, -1 for bad arguments (an IDAT beyond 2^31 - 1 bytes
+ *     included), -2 if out_cap is too small (65 bytes and every piece).  Host only.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_PREVIEW_MAX_PX 4096
+typedef struct { int32_t sample, set, first, count; } pca_preview_polyline;
+int64_t pca_preview_stream_bytes(int32_t px);
+int64_t pca_preview_workspace_bytes(int32_t k, int32_t px);
+int pca_preview_sheets(pca_ctx *ctx, const void *planes /*dev*/, int32_t k, int32_t px, const int32_t *verts /*dev*/, int64_t n_verts,
+                       const pca_preview_polyline *polylines /*dev*/, int32_t n_polylines, const uint8_t *lut /*dev*/,
+                       const float *ranges /*host*/, int32_t filter, void *out_stream /*dev*/, void *workspace /*dev*/, void *stream);
+int pca_adler32_chunks(pca_ctx *ctx, const void *src /*dev*/, const pca_deflate_chunk *chunk_table /*dev*/, int64_t n_chunks,
+                       uint32_t *out /*dev*/, void *stream);
+uint32_t pca_host_adler32_combine(uint32_t adler_a, uint32_t adler_b, int64_t len_b);
+int64_t pca_host_png_assemble(int32_t width, int32_t height, int32_t n_pieces, const void *const *piece, const int64_t *piece_bytes,
+                              uint32_t adler, void *out, int64_t out_cap);
+
+/* ------------------------------------------------------------------------------------------------
  * Host helper (no device work): the accumulator's pose track -- the per-frame bookkeeping integrate() does on Python
  * lists in the reference.  Replaces sem_pc_accum.py:156-165 (update_poses), :185-209 (remove_observations), :211-228
  * (comp_incr_path_dist), :404-415 (dist) and, for runners that replay it, the sample trigger of

@@ -41,6 +41,11 @@ def _writer():
     return writer
 
 
+def _preview():
+    from pca_amd import preview
+    return preview
+
+
 class LazyBev(dict):
     """The reference's BEV dict whose plane arrays are still on their way from the device: the fp16 D2H copy was
     enqueued on a side stream into pinned memory; the first access waits for THAT copy only and fills the dict in.
@@ -64,6 +69,12 @@ class LazyBev(dict):
         keep = getattr(event, 'keep', None)
         if keep and _writer().device_codec_selected():
             self._dev = (keep[0], index)
+        # while PCA_VIZ=device (pca_amd.preview): a reference of its own for the preview sheet -- (the device planes, the
+        # sample's index, the trajectories of every sample of the block or None) -- kept until the preview has been enqueued
+        # or the sample dies, whatever the writer's codec does with `_dev`
+        self._dev_preview = None
+        if keep and _preview().selected():
+            self._dev_preview = (keep[0], index, None)
         self._zero_copy = LazyBev._live[0] < LazyBev.MAX_PINNED_LIVE
         if self._zero_copy:
             import weakref
@@ -355,8 +366,13 @@ class SemBEVGenerator(BEVGenerator):
             ctx.check(ticket)
         assert planes.is_contiguous()
         event = _PendingCopy(ctx, ticket, (planes, host))
-        return [LazyBev(host, i, event, (r['trajs_present'], r['trajs_future'], r['trajs_full']), r.get('gt_lanes'))
+        bevs = [LazyBev(host, i, event, (r['trajs_present'], r['trajs_future'], r['trajs_full']), r.get('gt_lanes'))
                 for i, r in enumerate(results)]
+        block = [b._pending[3] for b in bevs]
+        for b in bevs:
+            if b._dev_preview is not None:   # one sheet job renders the block: it needs every sample's trajectories
+                b._dev_preview = b._dev_preview[:2] + (block, )
+        return bevs
 
     @staticmethod
     def warp_planes_device(p16, a_1, a_2, b_1, b_2, out16=None):
@@ -429,7 +445,17 @@ class SemBEVGenerator(BEVGenerator):
 
     # ------------------------------------------------------------------------------------------
     def viz_bev(self, bev, file_path, rgbs=[], semsegs=[]):
-        """Writes a PNG overview of one BEV sample (plot layout is not part of the parity contract)."""
+        """Writes a PNG overview of one BEV sample (plot layout is not part of the parity contract).
+        PCA_VIZ=device: the sample's preview sheet, rendered and compressed on the device and written by the shared
+        background writer (pca_amd.preview: 3 x 5 panels and the trajectories; `rgbs`, `semsegs`, gt_lanes and extra
+        sem_planes are not drawn); PCA_ASYNC_WRITE=0 waits for the file.  Default (PCA_VIZ=matplotlib): the figure below."""
+        if _preview().selected():
+            import os
+            w = _writer().shared_writer()
+            w.submit_preview(bev, file_path)
+            if os.environ.get('PCA_ASYNC_WRITE', '1') == '0':
+                _writer().flush_shared()
+            return
         import matplotlib
         matplotlib.use('Agg')
         import matplotlib.pyplot as plt

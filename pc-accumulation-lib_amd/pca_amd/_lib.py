@@ -29,6 +29,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
            'pca_host_track_step', 'pca_host_track_trigger', 'pca_host_stage_h2d', 'pca_host_d2h_async', 'pca_host_d2h_wait',
            'pca_deflate_workspace_bytes', 'pca_deflate_chunks', 'pca_deflate_chunks_dyn', 'pca_host_crc32_combine', 'pca_host_gzip_assemble',
+           'pca_preview_stream_bytes', 'pca_preview_workspace_bytes', 'pca_preview_sheets', 'pca_adler32_chunks', 'pca_host_adler32_combine', 'pca_host_png_assemble',
            'pca_kitti_integrate', 'pca_kitti_generate_bev', 'pca_k1_defer', 'pca_k1_flush', 'pca_host_camera_cone', 'pca_host_view_hull', 'pca_bev_bin_range', 'pca_bev_view_hint', 'pca_kitti_integrate_v', 'pca_kitti_generate_bev_v', 'pca_f32_box_decode', 'pca_debug_bev_level1', 'pca_debug_icp_layout',
            'pca_profile_enable', 'pca_profile_read')
 
@@ -245,6 +246,17 @@ def load():
     lib.pca_host_crc32_combine.restype = C.c_uint32
     lib.pca_host_gzip_assemble.argtypes = [i32, vp, vp, vp, vp, vp, i64]
     lib.pca_host_gzip_assemble.restype = i64
+    lib.pca_preview_stream_bytes.argtypes = [i32]
+    lib.pca_preview_stream_bytes.restype = i64
+    lib.pca_preview_workspace_bytes.argtypes = [i32, i32]
+    lib.pca_preview_workspace_bytes.restype = i64
+    # (polylines: device address of records laid out like pca_preview_polyline = preview.POLYLINE_DTYPE; ranges: host floats)
+    lib.pca_preview_sheets.argtypes = [vp, vp, i32, i32, vp, i64, vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.pca_adler32_chunks.argtypes = [vp, vp, vp, i64, vp, vp]
+    lib.pca_host_adler32_combine.argtypes = [C.c_uint32, C.c_uint32, i64]
+    lib.pca_host_adler32_combine.restype = C.c_uint32
+    lib.pca_host_png_assemble.argtypes = [i32, i32, i32, vp, vp, C.c_uint32, vp, i64]
+    lib.pca_host_png_assemble.restype = i64
     lib.pca_kitti_integrate.argtypes = [vp, C.POINTER(PcaKittiObs), C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_uint64),
                                         C.POINTER(PcaStore), vp, i32, i32, vp, vp, C.c_double, C.POINTER(C.c_int64),
                                         C.POINTER(C.c_double), vp]

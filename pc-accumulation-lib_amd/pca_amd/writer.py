@@ -10,7 +10,11 @@ member (pca_host_gzip_assemble).  The file inflates to exactly pickle.dumps(dict
 
 huffman='dynamic' (opt-in on top of the device codec; PCA_WRITER_HUFFMAN=dynamic for the shared writer) compresses with
 pca_deflate_chunks_dyn: the same tokens, each chunk with a Huffman code of its own where that is smaller.  Same pieces,
-same splice, smaller files."""
+same splice, smaller files.
+
+submit_preview (PCA_VIZ=device routes viz_bev here) writes a sample's preview sheet as a PNG the same way: the sheet is
+rendered, filtered and compressed on the device (pca_amd/preview.py), once per block of planes; the worker threads assemble
+the container and write the file."""
 import atexit
 import ctypes as C
 import gzip
@@ -235,6 +239,14 @@ def splice_sample(blob, found, layout, sizes, crcs, data):
     return gzip_assemble(pieces)
 
 
+class _PreviewItem:
+    """One preview sheet on its way through the writer: sample `index` of the sheet job `job`, to be written to `path`."""
+    __slots__ = ('job', 'index', 'path')
+
+    def __init__(self, job, index, path):
+        self.job, self.index, self.path = job, index, path
+
+
 class _Item:
     """One sample on its way through the writer.  job is None: the host codec takes it (bev is a plain dict by the time a
     worker sees it, unless it is the device_only form).  Else: sample `index` of that device job, meta = what
@@ -263,6 +275,9 @@ class AsyncBevWriter:
         self._refill = []                    # samples a worker handed back: filled in on the submitting thread, then host codec
         self._jobs = {}                      # id(planes block) -> its device job, while the block lives
         self._parked = None
+        self._preview_jobs = {}              # id(planes block) -> its sheet job, while the block lives
+        self._parked_preview = None
+        self.previews_written = 0
         self._open = True
         if codec == 'device':
             _device_writers[0] += 1
@@ -307,12 +322,23 @@ class AsyncBevWriter:
         with self._lock:
             self.device_written += 1
 
+    def _write_preview(self, it):
+        png = it.job.png(it.index)
+        os.makedirs(os.path.dirname(os.path.abspath(it.path)), exist_ok=True)
+        with open(it.path, 'wb') as f:
+            f.write(png)
+        with self._lock:
+            self.previews_written += 1
+
     def _work(self):
         while True:
             it = self.q.get()
             if it is None:
                 return
             try:
+                if type(it) is _PreviewItem:
+                    self._write_preview(it)
+                    continue
                 os.makedirs(it.write_dir, exist_ok=True)
                 if it.job is not None:
                     self._write_device(it)
@@ -412,6 +438,47 @@ class AsyncBevWriter:
             it.bev = dict(it.bev)
         self.q.put(it)
 
+    # ---- preview sheets (pca_amd/preview.py)
+    @staticmethod
+    def _preview_source(bev):
+        """(planes block [k,21,px,px] on the device, index of the sample in it, the block's trajectories), from the device
+        planes a LazyBev made under PCA_VIZ=device has kept or, for any other sample, from its 15 arrays uploaded."""
+        import torch
+        from .preview import SETS, planes_of
+        dev = getattr(bev, '_dev_preview', None)
+        if dev is not None and dev[0].is_cuda and dev[0].is_contiguous():
+            planes, index, block = dev
+            if planes.dim() == 4 and block is not None and len(block) == planes.shape[0]:
+                return planes, index, block
+            # a sample on its own, or one whose siblings are unknown: a job of one (its trajectories without waiting for its copy)
+            own = bev._pending[3] if bev._pending is not None else tuple(bev[f'trajs_{s}'] for s in SETS)
+            one = planes if planes.dim() == 3 else planes[index]
+            return one.view((1, ) + tuple(one.shape)), 0, [tuple(own)]
+        host = planes_of(bev)
+        return torch.from_numpy(host).cuda().view((1, ) + host.shape), 0, [tuple(bev[f'trajs_{s}'] for s in SETS)]
+
+    def submit_preview(self, bev, file_path):
+        """The preview sheet of `bev` (a LazyBev, or the reference's dict of host arrays) as the PNG `file_path`.  The
+        kernels are enqueued here, on the thread that talks to HIP, once per block of planes (the samples of a
+        generate_bev_many or bev_num > 1 share the job); the preview is parked like a sample and released -- waited for
+        and queued -- by the next preview, flush or close; the worker threads assemble the container and write the file."""
+        from .preview import SheetJob
+        self._release_parked_preview()
+        planes, index, block = self._preview_source(bev)
+        job = self._preview_jobs.get(id(planes))
+        if job is None or job.planes_ref() is not planes:
+            self._preview_jobs = {k: j for k, j in self._preview_jobs.items() if j.planes_ref() is not None}
+            job = self._preview_jobs[id(planes)] = SheetJob(planes, block)
+        if getattr(bev, '_dev_preview', None) is not None:
+            bev._dev_preview = None          # enqueued: the job holds the planes from here on
+        self._parked_preview = _PreviewItem(job, index, file_path)
+
+    def _release_parked_preview(self):
+        it, self._parked_preview = self._parked_preview, None
+        if it is not None:
+            it.job.wait()
+            self.q.put(it)
+
     def _take_refills(self):
         """Samples the workers could not splice: filled in here, on the submitting thread, and queued for the host codec."""
         with self._lock:
@@ -422,6 +489,7 @@ class AsyncBevWriter:
 
     def flush(self):
         self._release_parked()
+        self._release_parked_preview()
         self.q.join()
         while self._take_refills():
             self.q.join()
