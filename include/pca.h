@@ -435,6 +435,45 @@ int pca_bev_elev_partition(pca_ctx *ctx, const pca_store *store, const int64_t *
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The BEV window voxelised into semantic occupancy labels: the grid with a height axis, a majority vote per voxel (what
+ *       SemanticKITTI-SSC / SSCBench-KITTI-360 labels are made from).  No reference counterpart: an extension on the
+ *       scaffold of the two passes above.  The geometry is that of pca_bev_elev_partition (owed re-transforms oldest first,
+ *       origin, R, dx / dy, strict crop, z < height_filter, floor to the grid, clamp, image rows; a point whose z is not
+ *       finite is dropped).
+ *     include_dyn == 0: points with dyn == 1 are dropped; include_dyn != 0: they take part.
+ *     label_of (host, 256 bytes): the label of a kept point is label_of[its class byte]; 255: the point takes no part;
+ *       any other value must be < n_labels.  Several classes may share a label.
+ *     Height bin: z = (Z - origin z) + 0.0, t = (z - z_lo) / z_step, k = floor(t), all f64, the division IEEE.  A point
+ *       is kept iff 0 <= k < nz: in z NOTHING is clamped, a point below z_lo or at or above z_lo + nz z_step is dropped.
+ *     Per voxel (k, row, col) with n_l kept points of label l:  counts = sum n_l,  top = max n_l,  labels = the smallest l
+ *       with n_l == top, 255 where counts == 0.  The counters are 32 bits wide.
+ *     Output (dev, any of them may be NULL, not all): labels u8, counts u32, top u32, each [nz][px][px].
+ *     Scope: an EMPTY voxel is one no kept point fell into.  Whether it is free space or merely unseen is not decided
+ *       here: there is no ray casting.
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
+ *     Limits: 1 <= px <= 1024 (else "bev voxel labels: px must be in 1..1024": no banding), 1 <= nz <= 32,
+ *       1 <= n_labels <= 32; z_lo finite; z_step finite and > 0.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to what is read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a bin range
+ *     armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared (the whole window is read).  A window above
+ *     max_points is cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives labels 255, counts 0 and
+ *     top 0.  Every argument is checked before anything is launched; -1 with pca_last_error set.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_BEV_VOXEL_MAX_Z 32
+#define PCA_BEV_VOXEL_MAX_LABELS 32
+int64_t pca_bev_voxel_workspace_bytes(int64_t max_points, int px);
+int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                         int slot_begin, int slot_end, int64_t max_points,
+                         const pca_bev_params *prm, double z_lo, double z_step, int nz,
+                         const uint8_t label_of[256] /*host*/, int n_labels, int include_dyn,
+                         const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                         void *workspace /*dev*/, int64_t workspace_bytes,
+                         uint8_t  *labels /*dev [nz][px][px] or NULL*/,
+                         uint32_t *counts /*dev [nz][px][px] or NULL*/,
+                         uint32_t *top    /*dev [nz][px][px] or NULL*/,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -772,7 +811,8 @@ int64_t pca_host_track_trigger(pca_host_track *t, double bev_horizon, int64_t pr
 enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
     PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
-    PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS, PCA_K_COUNT
+    PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS,
+    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

@@ -318,6 +318,51 @@ class SemBEVGenerator(BEVGenerator):
         st.load_rows([pc])
         return st.bev_elev_partition(prm, elev_thresh, include_dyn=include_dyn)
 
+    # ---- semantic occupancy labels (extension: pca_bev_voxel_labels) -------------------------------
+    @staticmethod
+    def voxel_label_table(classes=None):
+        """(label_of uint8 [256], n_labels) of `classes`: a list of class-index lists, list i becomes label i (a class named
+        in two lists is a ValueError); None: label = class for the classes 0 .. 31.  Every other class is ignored (255)."""
+        table = np.full(256, 255, dtype=np.uint8)
+        if classes is None:
+            table[:32] = np.arange(32)
+            return table, 32
+        if not 1 <= len(classes) <= 32:
+            raise ValueError('classes: 1 to 32 lists of classes')
+        for label, group in enumerate(classes):
+            for c in group:
+                c = int(c)
+                if not 0 <= c <= 255:
+                    raise ValueError(f'classes: {c} is not a class byte')
+                if table[c] != 255:
+                    raise ValueError(f'classes: class {c} is named in two lists')
+                table[c] = label
+        return table, len(classes)
+
+    def voxel_labels_device(self, pc, rot_mat, dx, dy, aug_view_size, z_range, nz, classes=None, include_dyn=False):
+        """One point set voxelised into semantic occupancy labels, in the frame the 21 planes are rasterised in, with nz
+        height bins over z_range = (lo, hi) metres of that frame (DeviceStore.bev_voxel_labels: the dict of cuda tensors
+        'labels', 'counts', 'top', each [nz, px, px]).  pc: a WindowPart or host rows in BEV-frame metres.  classes: see
+        voxel_label_table (sem_idxs names are taken too)."""
+        lo, hi = float(z_range[0]), float(z_range[1])
+        nz = int(nz)
+        z_step = (hi - lo) / nz if nz > 0 else float('nan')
+        if classes is not None:
+            classes = [self._classes_of(g) for g in classes]
+        table, n_labels = self.voxel_label_table(classes)
+        if isinstance(pc, WindowPart):
+            w = pc.window
+            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
+            if w.future_is_present:
+                f0, f1 = w.first, w.last
+            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
+            return w.store.bev_voxel_labels(prm, lo, z_step, nz, table, n_labels, first_frame=f0, last_frame=f1,
+                                            include_dyn=include_dyn)
+        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
+        st = self._tmp_store('voxel')
+        st.load_rows([pc])
+        return st.bev_voxel_labels(prm, lo, z_step, nz, table, n_labels, include_dyn=include_dyn)
+
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the
         partition column).  Builds the minimum-z map of ALL the rows (no static partition, no height filter: the method

@@ -1,5 +1,5 @@
-// pca_bev_side.h -- the scaffold of the two side passes over the BEV window (the class planes pca_bev_class.hip, the elevation
-// partition pca_bev_elev.hip): two levels, LDS atomics only, no global atomics.
+// pca_bev_side.h -- the scaffold of the side passes over the BEV window (the class planes pca_bev_class.hip, the elevation
+// partition pca_bev_elev.hip, the occupancy labels pca_bev_voxel.hip): two levels, LDS atomics only, no global atomics.
 //
 //   level 1  side_bin<Policy>  1024 threads; workgroup g takes chunk g of the window: the policy's key of every point (owed
 //                              re-transforms, view test and cell: pca_bev_view.h), tile in the key's high bits; LDS histogram
@@ -21,7 +21,7 @@
 #define SIDE_PLACES (SIDE_MAX_G + 8)   // places of a table row at most
 #define SIDE_PX_MAX 1024
 
-struct SideArgs {                 // the first member of both passes' argument blocks
+struct SideArgs {                 // the first member of every pass's argument block
     pca_store st;
     const int64_t *frame_off;
     int slot_begin, slot_split, slot_end;
@@ -193,8 +193,8 @@ __device__ __forceinline__ int side_find(const uint32_t *s_pre, int places, uint
 
 // ---- host side ----
 static inline int side_tiles_x(int px) { return (px + TS - 1) / TS; }
-// env_name (PCA_BEV_CLASS_G / PCA_BEV_ELEV_G): a cap on level 1's workgroups, read on every call (tests set it to push chunks
-// beyond the register path)
+// env_name (PCA_BEV_CLASS_G / PCA_BEV_ELEV_G / PCA_BEV_VOXEL_G): a cap on level 1's workgroups, read on every call (tests set
+// it to push chunks beyond the register path)
 static inline int side_groups(int64_t max_points, const char *env_name)
 {
     const int max_g = (int)pca_env_int(env_name, SIDE_MAX_G, 1, SIDE_MAX_G);
@@ -219,7 +219,7 @@ static inline SideLayout side_layout(int64_t max_points, int px, int64_t record_
     l.total = l.tail + pca_align256((int64_t)l.T * tile_bytes) + 512;
     return l;
 }
-// The checks the two entry points share (each has checked its own pointers and slot order) and the common argument block;
+// The checks the entry points share (each has checked its own pointers and slot order) and the common argument block;
 // l: the pass's layout for (max_points, prm->px); `base`: the 256-byte aligned workspace its offsets count from.
 static inline int side_check(pca_ctx *ctx, const char *what, const pca_store *store, const int64_t *frame_off, int slot_begin,
                              int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm, const double *pending_Ts,

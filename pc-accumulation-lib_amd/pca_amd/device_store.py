@@ -53,8 +53,8 @@ class DeviceStore:
         self._ws = None
         self._ws_many = None
         self._ws_points, self._ws_px = 0, 0
-        # scratch of bev_class_planes and of bev_elev_partition, each its own (a main raster may have sized _ws differently):
-        # name -> [buffer, the points it is sized for, px], see _side_workspace
+        # scratch of bev_class_planes, of bev_elev_partition and of bev_voxel_labels, each its own (a main raster may have sized
+        # _ws differently): name -> [buffer, the points it is sized for, px], see _side_workspace
         self._ws_side = {}
         self._dedup_ws = None
         self._obs_out = None
@@ -597,12 +597,12 @@ class DeviceStore:
         self._k1_noted = None                      # (a raster takes a noted K1 along or runs it first: nothing is noted any more)
 
     def _side_workspace(self, name, workspace_bytes, max_points, px):
-        """The scratch of a side pass (bev_class_planes, bev_elev_partition), fit for max_points at `px`."""
+        """The scratch of a side pass (bev_class_planes, bev_elev_partition, bev_voxel_labels), fit for max_points at `px`."""
         ws = self._ws_side.setdefault(name, [None, 0, 0])
         if ws[0] is None or max_points > ws[1] or px != ws[2]:
             # sized with headroom so that a window growing frame by frame does not reallocate every call
             ws[1], ws[2] = int(max_points * 1.25) + 1, px
-        need = workspace_bytes(ws[1], px)              # (asked every call: PCA_BEV_CLASS_G / PCA_BEV_ELEV_G change it)
+        need = workspace_bytes(ws[1], px)              # (asked every call: PCA_BEV_CLASS_G / _ELEV_G / _VOXEL_G change it)
         if ws[0] is None or ws[0].numel() < need:
             ws[0] = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
         return ws[0]
@@ -679,6 +679,41 @@ class DeviceStore:
         if mark_dyn:
             self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
         return {'elev': elev, 'observed': obs.bool(), 'flags': flags, 'counts': counts}
+
+    def bev_voxel_labels(self, prm, z_lo, z_step, nz, label_of, n_labels, first_frame=0, last_frame=None, include_dyn=False,
+                         max_points=None):
+        """Live frames [first_frame, last_frame) voxelised into semantic occupancy labels (pca_bev_voxel_labels): the grid of
+        `prm` with nz height bins of z_step metres from z_lo (z in the BEV frame; outside the range a point is dropped, not
+        clamped), a majority vote per voxel.  label_of: 256 entries, class -> label below n_labels, 255 = the class takes
+        no part.  include_dyn=False: points with dyn == 1 take no part.
+        Returns a dict of cuda tensors, each [nz, px, px], image rows: 'labels' uint8, the smallest label among the most
+        frequent ones (255: an empty voxel -- free or unseen is not decided, there is no ray casting); 'counts' and 'top'
+        int32 holding the u32 numbers of labelled points and of points of the winning label.
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        ctx, lib = self.ctx, self.ctx.lib
+        last_frame = self.n_frames if last_frame is None else last_frame
+        px = int(prm.px)
+        table = np.ascontiguousarray(label_of, dtype=np.uint8)
+        if table.shape != (256, ):
+            raise ValueError('label_of must hold 256 entries')
+        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
+        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+        bound = self.max_window_points()
+        max_points = bound if max_points is None else max(int(max_points), 1)
+        ws = self._side_workspace('voxel', lib.pca_bev_voxel_workspace_bytes, max_points, px)
+        shape = (max(int(nz), 1), max(px, 1), max(px, 1))
+        labels = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        counts = torch.empty(shape, dtype=torch.int32, device=self.device)
+        top = torch.empty(shape, dtype=torch.int32, device=self.device)
+        st = self.c_store()
+        ctx.check(lib.pca_bev_voxel_labels(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
+                                           self.head + last_frame, max_points, C.byref(prm), float(z_lo), float(z_step),
+                                           int(nz), table.ctypes.data, int(n_labels), 1 if include_dyn else 0, pend_T,
+                                           pend_ends, n_pend, ws.data_ptr(), ws.numel(), labels.data_ptr(),
+                                           counts.data_ptr(), top.data_ptr(), ctx.stream()))
+        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        return {'labels': labels, 'counts': counts, 'top': top}
 
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters

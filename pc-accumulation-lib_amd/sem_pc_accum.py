@@ -341,6 +341,23 @@ class SemanticPointCloudAccumulator:
         return gen.elev_partition_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, elev_thresh,
                                          include_dyn=False, mark_dyn=mark_dyn)
 
+    def voxel_labels(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False):
+        """Extension (no reference counterpart): semantic occupancy labels of `part` ('present' | 'future' | 'full') of the
+        sample generate_bev(present_idx, 1, True) would make, in that sample's un-augmented frame (heading from the last
+        two present poses, no shift, zoom 1): the sample's grid with nz height bins over z_range metres, a majority vote
+        over the labelled points of every voxel.  classes: a list of class lists, list i becomes label i; None: label =
+        class for the classes 0 .. 31.  Returns DeviceStore.bev_voxel_labels' dict of cuda tensors 'labels', 'counts',
+        'top', each [nz, px, px]; labels 255 = no point in the voxel (free or unseen is not decided: no ray casting).
+        Nothing is written: the store, the owed re-transforms and every later sample stay as they are."""
+        if part not in ('present', 'future', 'full'):
+            raise ValueError("part must be 'present', 'future' or 'full'")
+        gen = self.sem_bev_generator
+        self.store.poll_status()
+        pcs, trajs = self._window_inputs_for(present_idx, True)
+        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
+        return gen.voxel_labels_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, classes=classes,
+                                       include_dyn=include_dyn)
+
     def generate_bev_many(self, present_idxs, gen_future: bool = True):
         """Extension (no reference counterpart): the samples generate_bev(idx, 1, gen_future)[0] would return for every idx of
         `present_idxs`, rasterised in ONE launch of each kernel (the store does not change between them: the driver's sweep
