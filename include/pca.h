@@ -449,7 +449,7 @@ int pca_bev_elev_partition(pca_ctx *ctx, const pca_store *store, const int64_t *
  *       with n_l == top, 255 where counts == 0.  The counters are 32 bits wide.
  *     Output (dev, any of them may be NULL, not all): labels u8, counts u32, top u32, each [nz][px][px].
  *     Scope: an EMPTY voxel is one no kept point fell into.  Whether it is free space or merely unseen is not decided
- *       here: there is no ray casting.
+ *       here: pca_bev_voxel_rays (below) casts the rays and tells the two apart.
  *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
  *     Limits: 1 <= px <= 1024 (else "bev voxel labels: px must be in 1..1024": no banding), 1 <= nz <= 32,
  *       1 <= n_labels <= 32; z_lo finite; z_step finite and > 0.
@@ -472,6 +472,52 @@ int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *fr
                          uint32_t *counts /*dev [nz][px][px] or NULL*/,
                          uint32_t *top    /*dev [nz][px][px] or NULL*/,
                          void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Lidar rays cast through the voxel grid of pca_bev_voxel_labels: which voxels a beam crossed on its way from the sensor to
+ *       a stored point.  With the labels' counts: occupied (counts > 0), else free (seen), else unseen -- the "invalid" mask
+ *       of SemanticKITTI-SSC / SSCBench-KITTI-360 ground truth.  No reference counterpart.  One ray per stored point of the
+ *       window, from the sensor position of its slot (origins, one per slot, in the store's CURRENT coordinates: the pose
+ *       track; they owe nothing) to the point (owed re-transforms applied, oldest first).
+ *     Everything is f64, each operation rounded on its own, nothing fused; the product sum is deliberately UNFUSED (unlike
+ *       the view test of the passes above), the divisions are IEEE.  Grid coordinates of a position (X, Y, Z):
+ *         x = X - ox, y = Y - oy;  ax = (r0 x + r1 y) + dx,  ay = (r3 x + r4 y) + dy;
+ *         u = ax / view * px + 0.5 px,  v = ay / view * px + 0.5 px,  w = (((Z - oz) + 0.0) - z_lo) / z_step.
+ *       Its voxel is (i, j, k) = (floor u, floor v, floor w), unclamped; inside the grid iff 0 <= i, j < px and 0 <= k < nz;
+ *       its place in the output is [k][px - 1 - j][i] (image rows).
+ *     Every point of the window casts a ray, except a point with dyn == 1 when include_dyn == 0.  The crop, height_filter
+ *       and the class play no part: a beam to a point outside the view or above the filter still crossed the grid.
+ *     A ray whose start or end has a grid coordinate that is not finite or is >= 2^30 in magnitude is dropped (stats[2]).
+ *       With start voxel c, end voxel g and n_a = |g_a - c_a|, a ray whose N = n_0 + n_1 + n_2 exceeds
+ *       PCA_BEV_RAYS_MAX_STEPS is dropped (stats[3]): the cap is a condition, it bounds every launch.
+ *     Traversal (Amanatides-Woo, driven by the integer step counts, so that it always ends in the end voxel), axes in the
+ *       order (u, v, w): d_a = e_a - s_a, step_a = sign(g_a - c_a); for n_a > 0: tMax_a = ((c_a + (step_a > 0 ? 1 : 0)) -
+ *       s_a) / d_a, tDelta_a = 1 / |d_a|, else tMax_a = +inf.  N times: mark the current voxel if it is inside the grid;
+ *       a = 0 if t0 <= t1 && t0 <= t2, else 1 if t1 <= t2, else 2; c_a += step_a, n_a -= 1; tMax_a = n_a ? tMax_a +
+ *       tDelta_a : +inf.  The end voxel is never marked by its own ray; a ray with N = 0 marks nothing.
+ *     Output (dev, either may be NULL, not both; both are cleared by the call itself, on the stream):
+ *       seen u8 [nz][px][px]: 1 = at least one ray passed through, else 0;
+ *       stats i64 [4]: points considered, rays cast (not dropped), dropped not finite, dropped too long.
+ *     Scope: ONE origin per stored frame (the merged sweeps of a NuScenes sample share their key frame's origin); no
+ *       per-beam minimum or maximum range.
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view and px are read.
+ *     Limits: 1 <= px <= 1024 (else "bev voxel rays: px must be in 1..1024"), 1 <= nz <= 32; z_lo finite; z_step finite
+ *       and > 0; slot_begin <= slot_end.  No workspace.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to the points that are read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a
+ *     bin range armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared.  A window above max_points is
+ *     cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives all zeros.  Every argument is checked
+ *     before anything is launched; -1 with pca_last_error set.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_BEV_RAYS_MAX_STEPS 16384
+int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                       int slot_begin, int slot_end, int64_t max_points,
+                       const pca_bev_params *prm, double z_lo, double z_step, int nz, int include_dyn,
+                       const double *origins /*dev [slot_end - slot_begin][3]: sensor position of each slot, store coordinates, current (nothing owed)*/,
+                       const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                       uint8_t *seen  /*dev [nz][px][px]: 1 = at least one ray passed through, else 0; or NULL*/,
+                       int64_t *stats /*dev [4]: points considered, rays cast, dropped not finite, dropped too long; or NULL*/,
+                       void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
@@ -812,7 +858,7 @@ enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
     PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
     PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS,
-    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_COUNT
+    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

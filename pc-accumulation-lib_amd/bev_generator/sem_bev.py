@@ -363,6 +363,31 @@ class SemBEVGenerator(BEVGenerator):
         st.load_rows([pc])
         return st.bev_voxel_labels(prm, lo, z_step, nz, table, n_labels, include_dyn=include_dyn)
 
+    # ---- rays through the voxel grid: free against unseen (extension: pca_bev_voxel_rays) ------------
+    def voxel_rays_device(self, pc, origins, rot_mat, dx, dy, aug_view_size, z_range, nz, include_dyn=False):
+        """One lidar ray per point, from the sensor position of the point's frame to the point, cast through the grid of
+        voxel_labels_device (same frame, same z_range and nz): DeviceStore.bev_voxel_rays' dict of cuda tensors 'seen'
+        (uint8 [nz, px, px], 1 = a ray passed through) and 'stats' (int64 [4]).  pc: a WindowPart, with `origins`
+        [frames, 3] the sensor positions of exactly that part's frames in the store's coordinates; or a list of per-frame
+        host row arrays in BEV-frame metres, with one origin each in the same frame."""
+        lo, hi = float(z_range[0]), float(z_range[1])
+        nz = int(nz)
+        z_step = (hi - lo) / nz if nz > 0 else float('nan')
+        if isinstance(pc, WindowPart):
+            w = pc.window
+            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
+            if w.future_is_present:
+                f0, f1 = w.first, w.last
+            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
+            return w.store.bev_voxel_rays(prm, lo, z_step, nz, origins, first_frame=f0, last_frame=f1, include_dyn=include_dyn)
+        if isinstance(pc, np.ndarray):
+            raise ValueError('voxel_rays_device: host rows come as a list of per-frame arrays, one origin each')
+        frames = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in pc]
+        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
+        st = self._tmp_store('rays')
+        st.load_rows(frames)
+        return st.bev_voxel_rays(prm, lo, z_step, nz, origins, include_dyn=include_dyn)
+
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the
         partition column).  Builds the minimum-z map of ALL the rows (no static partition, no height filter: the method

@@ -1,0 +1,223 @@
+// pca_bev_rays.hip -- lidar rays cast through the voxel grid of the occupancy labels (pca_bev_voxel.hip): which voxels a beam
+// crossed on its way from the sensor to a stored point.  With the labels' counts this tells an empty voxel apart into free
+// (a beam passed) and unseen (none did) -- the "invalid" mask of SemanticKITTI-SSC / SSCBench-KITTI-360 ground truth.
+//
+//   bev_voxel_rays   one thread per stored point of the window, 256 threads, a grid-stride loop over chunks of 256 points.
+//                    The slot of a chunk's first point by a binary search over frame_off in scalar loads (the chunk is
+//                    workgroup-uniform), a lane's own slot by walking on from there; the slot's sensor position and the
+//                    point (owed re-transforms applied: pca_bev_view.h) into grid coordinates -- f64, nothing fused, the
+//                    IEEE divisions, the UNFUSED product sum (unlike the view test: a numpy model restates it bit for bit);
+//                    Amanatides-Woo driven by the integer step counts, so that it always ends in the end voxel, which is
+//                    not marked.  A mark is a byte load and, where that reads 0, a byte store of 1 into the u8 volume
+//                    [nz][px][px] (2 MiB at 256^2 x 32: it stays in L2): every writer writes the same value, so no atomic
+//                    is needed and the result does not depend on the order; a stale 0 from another CU's store costs one
+//                    redundant store.  The byte is looked at one step later, beside the next step's arithmetic (1.56 ms
+//                    against 1.62 on the headline window; ALWAYS_STORE, every mark a store without the load: 1.69 ms --
+//                    profiles/bev_voxel_rays.txt).  A ray leaves its loop early only by integer tests that cannot change
+//                    the marked set.  The four counters: per lane, per wave, LDS, one global add per counter and workgroup.
+// The store is never written.  PCA_BEV_RAYS_MAX_STEPS bounds every ray, hence every launch.
+#include "pca_bev_view.h"
+
+#define RAY_THREADS 256
+#define RAY_MAX_G 2048            // workgroups at most (eight per CU; the registers let six of them be resident)
+#define RAY_COORD_LIM 1073741824.0   // 2^30: a grid coordinate at or above it in magnitude drops the ray
+
+struct alignas(16) RayArgs {
+    pca_store st;
+    const int64_t *frame_off;
+    int slot_begin, slot_end;
+    int64_t max_points;
+    pca_bev_params prm;
+    BevOwed owed;                 // owed re-transforms: applied to the points that are read, never written back
+    double z_lo, z_step;
+    int nz, include_dyn;
+    int G;                        // workgroups of the launch
+    const double *origins;        // [slot_end - slot_begin][3]: the sensor position of each slot (nothing owed)
+    uint8_t *seen;                // [nz][px][px] or NULL
+    unsigned long long *stats;    // [4] or NULL
+    uint32_t *status;             // context status word (PCA_STATUS_* bits)
+};
+
+struct RayGrid { double ox, oy, oz, r0, r1, r3, r4, dx, dy, view, pxd, half_px, z_lo, z_step; };
+// grid coordinates of a position: each operation rounded on its own (-ffp-contract=off), the sums unfused
+__device__ __forceinline__ void ray_coords(const RayGrid &q, double X, double Y, double Z, double &u, double &v, double &w)
+{
+    const double x = X - q.ox, y = Y - q.oy;
+    const double ax = (q.r0 * x + q.r1 * y) + q.dx;
+    const double ay = (q.r3 * x + q.r4 * y) + q.dy;
+    u = ax / q.view * q.pxd + q.half_px;
+    v = ay / q.view * q.pxd + q.half_px;
+    w = (((Z - q.oz) + 0.0) - q.z_lo) / q.z_step;
+}
+__device__ __forceinline__ bool ray_coord_ok(double t) { return fabs(t) < RAY_COORD_LIM; }   // (false for NaN)
+
+template <bool ALWAYS_STORE>
+__global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
+{
+    __shared__ unsigned long long s_stat[4];
+    const int tid = (int)threadIdx.x;
+    if (tid < 4) s_stat[tid] = 0;
+    __syncthreads();
+    const int64_t lo = pca_sload(a.frame_off + a.slot_begin);
+    const int64_t hi0 = pca_sload(a.frame_off + a.slot_end);
+    int64_t hi = (hi0 - lo > a.max_points) ? lo + a.max_points : hi0;
+    if (hi > a.st.capacity) hi = a.st.capacity;            // (nothing is stored behind the capacity, whatever frame_off counts)
+    if (blockIdx.x == 0 && tid == 0 && hi0 - lo > a.max_points) pca_raise(a.status, PCA_STATUS_STORE_OVERFLOW);
+    const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
+    RayGrid q;
+    q.ox = a.prm.origin[0]; q.oy = a.prm.origin[1]; q.oz = a.prm.origin[2];
+    q.r0 = a.prm.R[0]; q.r1 = a.prm.R[1]; q.r3 = a.prm.R[3]; q.r4 = a.prm.R[4];
+    q.dx = a.prm.dx; q.dy = a.prm.dy; q.view = a.prm.view;
+    q.pxd = (double)a.prm.px; q.half_px = 0.5 * q.pxd;
+    q.z_lo = a.z_lo; q.z_step = a.z_step;
+    const int px = a.prm.px, nz = a.nz;
+    auto *seen = reinterpret_cast<__attribute__((address_space(1))) uint8_t *>(reinterpret_cast<uintptr_t>(a.seen));
+    const double INF = __builtin_huge_val();
+    uint32_t n_considered = 0, n_cast = 0, n_not_finite = 0, n_too_long = 0;
+
+    for (int64_t c_lo = lo + (int64_t)blockIdx.x * RAY_THREADS; c_lo < hi; c_lo += (int64_t)a.G * RAY_THREADS) {
+        // the slot of the chunk's first point: the last one with frame_off[slot] <= c_lo (scalar: the chunk is uniform)
+        int s_lo = a.slot_begin, s_hi = a.slot_end;
+        while (s_hi - s_lo > 1) {
+            const int mid = (s_lo + s_hi) >> 1;
+            if (pca_sload(a.frame_off + mid) <= c_lo) s_lo = mid; else s_hi = mid;
+        }
+        const int64_t p = c_lo + tid;
+        if (p >= hi) continue;
+        // the lane's own slot (p < hi <= frame_off[slot_end]: the walk ends below slot_end; empty frames are stepped over)
+        int slot = s_lo;
+        while (slot + 1 < a.slot_end && pca_ldg(a.frame_off + slot + 1) <= p) ++slot;
+        if (!a.include_dyn && pca_ldg(a.st.dyn + p) == 1) continue;
+        ++n_considered;
+        double X = pca_ldg(a.st.x + p), Y = pca_ldg(a.st.y + p), Z = pca_ldg(a.st.z + p);
+        apply_owed(a.owed, pend_hi, p, X, Y, Z);
+        const double *o = a.origins + (int64_t)(slot - a.slot_begin) * 3;
+        double s0, s1, s2, e0, e1, e2;
+        ray_coords(q, pca_ldg(o), pca_ldg(o + 1), pca_ldg(o + 2), s0, s1, s2);
+        ray_coords(q, X, Y, Z, e0, e1, e2);
+        if (!(ray_coord_ok(s0) && ray_coord_ok(s1) && ray_coord_ok(s2) && ray_coord_ok(e0) && ray_coord_ok(e1) && ray_coord_ok(e2))) {
+            ++n_not_finite;
+            continue;
+        }
+        int c0 = (int)floor(s0), c1 = (int)floor(s1), c2 = (int)floor(s2);
+        const int g0 = (int)floor(e0), g1 = (int)floor(e1), g2 = (int)floor(e2);
+        int n0 = abs(g0 - c0), n1 = abs(g1 - c1), n2 = abs(g2 - c2);           // (each below 2^31: |c|, |g| <= 2^30)
+        const int64_t N64 = (int64_t)n0 + n1 + n2;
+        if (N64 > PCA_BEV_RAYS_MAX_STEPS) {
+            ++n_too_long;
+            continue;
+        }
+        ++n_cast;
+        // integer early exit 1: the ray's voxel bounding box misses the grid (or there is nothing to mark in)
+        if (!a.seen || (c0 < 0 && g0 < 0) || (c0 >= px && g0 >= px) || (c1 < 0 && g1 < 0) || (c1 >= px && g1 >= px) ||
+            (c2 < 0 && g2 < 0) || (c2 >= nz && g2 >= nz))
+            continue;
+        const int st0 = (g0 > c0) - (g0 < c0), st1 = (g1 > c1) - (g1 < c1), st2 = (g2 > c2) - (g2 < c2);
+        const double d0 = e0 - s0, d1 = e1 - s1, d2 = e2 - s2;
+        double t0 = INF, t1 = INF, t2 = INF, dl0 = 0.0, dl1 = 0.0, dl2 = 0.0;
+        if (n0 > 0) { t0 = ((double)(c0 + (st0 > 0 ? 1 : 0)) - s0) / d0; dl0 = 1.0 / fabs(d0); }
+        if (n1 > 0) { t1 = ((double)(c1 + (st1 > 0 ? 1 : 0)) - s1) / d1; dl1 = 1.0 / fabs(d1); }
+        if (n2 > 0) { t2 = ((double)(c2 + (st2 > 0 ? 1 : 0)) - s2) / d2; dl2 = 1.0 / fabs(d2); }
+        const int N = (int)N64;
+        // a mark's byte is looked at one step later (pm, pv: the byte of the step before and what the load gave), so that the
+        // load's round trip runs beside a whole step's arithmetic; pv = 1: nothing waits
+        auto *pm = seen;
+        uint8_t pv = 1;
+        for (int it = 0; it < N; ++it) {
+            auto *m = seen;
+            uint8_t v = 1;
+            if ((unsigned)c0 < (unsigned)px && (unsigned)c1 < (unsigned)px && (unsigned)c2 < (unsigned)nz) {
+                m = seen + ((size_t)c2 * px + (size_t)(px - 1 - c1)) * px + c0;
+                if (ALWAYS_STORE) *m = 1; else v = *m;
+            } else if ((c0 < 0 && st0 <= 0) || (c0 >= px && st0 >= 0) || (c1 < 0 && st1 <= 0) || (c1 >= px && st1 >= 0) ||
+                       (c2 < 0 && st2 <= 0) || (c2 >= nz && st2 >= 0)) {
+                break;                                      // integer early exit 2: outside on an axis and moving away, or not moving
+            }
+            if (pv == 0) *pm = 1;
+            pm = m; pv = v;
+            if (t0 <= t1 && t0 <= t2) {
+                c0 += st0; --n0;
+                t0 = n0 ? t0 + dl0 : INF;
+            } else if (t1 <= t2) {
+                c1 += st1; --n1;
+                t1 = n1 ? t1 + dl1 : INF;
+            } else {
+                c2 += st2; --n2;
+                t2 = n2 ? t2 + dl2 : INF;
+            }
+        }
+        if (pv == 0) *pm = 1;
+    }
+
+    // the counters: wave, LDS, one global add per counter
+    const uint32_t w_considered = wave_reduce_add(n_considered), w_cast = wave_reduce_add(n_cast);
+    const uint32_t w_not_finite = wave_reduce_add(n_not_finite), w_too_long = wave_reduce_add(n_too_long);
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_stat[0], (unsigned long long)w_considered);
+        atomicAdd(&s_stat[1], (unsigned long long)w_cast);
+        atomicAdd(&s_stat[2], (unsigned long long)w_not_finite);
+        atomicAdd(&s_stat[3], (unsigned long long)w_too_long);
+    }
+    __syncthreads();
+    if (tid < 4 && a.stats && s_stat[tid]) atomicAdd(a.stats + tid, s_stat[tid]);
+}
+
+extern "C" {
+
+int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off, int slot_begin, int slot_end,
+                       int64_t max_points, const pca_bev_params *prm, double z_lo, double z_step, int nz, int include_dyn,
+                       const double *origins, const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                       uint8_t *seen, int64_t *stats, void *stream)
+{
+    if (!ctx) return -1;
+    if (max_points < 1) max_points = 1;
+    hipStream_t s = (hipStream_t)stream;
+    // every check comes before the first launch (a noted K1 and the clearing of the outputs included)
+    if (!store || !frame_off || !prm || !origins || (!seen && !stats)) {
+        ctx->err = "bev voxel rays: bad arguments";
+        return -1;
+    }
+    if (!store->x || !store->y || !store->z || !store->dyn) {
+        ctx->err = "bev voxel rays: the store's x, y, z and dyn arrays are needed";
+        return -1;
+    }
+    if (prm->px < 1 || prm->px > 1024) { ctx->err = "bev voxel rays: px must be in 1..1024"; return -1; }
+    if (nz < 1 || nz > PCA_BEV_VOXEL_MAX_Z) { ctx->err = "bev voxel rays: nz must be in 1..32"; return -1; }
+    if (!(fabs(z_lo) < __builtin_huge_val())) { ctx->err = "bev voxel rays: z_lo must be finite"; return -1; }
+    if (!(z_step > 0.0 && z_step < __builtin_huge_val())) { ctx->err = "bev voxel rays: z_step must be finite and > 0"; return -1; }
+    if (bev_check_rotation(ctx, "bev voxel rays", prm)) return -1;
+    if (slot_begin > slot_end) { ctx->err = "bev voxel rays: need slot_begin <= slot_end"; return -1; }
+    RayArgs A;
+    if (bev_fill_owed(ctx, "bev voxel rays", pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, A.owed)) return -1;
+    A.st = *store;
+    A.frame_off = frame_off;
+    A.slot_begin = slot_begin; A.slot_end = slot_end;
+    A.max_points = max_points;
+    A.prm = *prm;
+    A.z_lo = z_lo; A.z_step = z_step;
+    A.nz = nz; A.include_dyn = include_dyn;
+    const int64_t chunks = (max_points + RAY_THREADS - 1) / RAY_THREADS;
+    // PCA_BEV_RAYS_G: a cap on the workgroups, read on every call (tests set it to send a workgroup round its loop again)
+    const int64_t max_g = pca_env_int("PCA_BEV_RAYS_G", RAY_MAX_G, 1, RAY_MAX_G);
+    A.G = (int)(chunks > max_g ? max_g : chunks);
+    A.origins = origins;
+    A.seen = seen;
+    A.stats = reinterpret_cast<unsigned long long *>(stats);
+    A.status = ctx->ticket + 1;
+    PCA_CHECK(ctx, hipSetDevice(ctx->device));
+    if (pca_k1_flush_pending(ctx)) return -1;               // a noted K1 runs on its own first, as before the occupancy labels
+    if (seen) PCA_CHECK(ctx, hipMemsetAsync(seen, 0, (size_t)nz * prm->px * prm->px, s));
+    if (stats) PCA_CHECK(ctx, hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), s));
+    const RayArgs &args = A;
+    if (slot_end > slot_begin)                              // (a window without a slot: no launch over zero points)
+    {
+        if (pca_env_int("PCA_BEV_RAYS_STORE", 0, 0, 1))     // A/B: 1 = every mark stores, without the load in front (same result)
+            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<true>, dim3(args.G), dim3(RAY_THREADS), s, args);
+        else
+            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<false>, dim3(args.G), dim3(RAY_THREADS), s, args);
+    }
+    PCA_CHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -687,7 +687,7 @@ class DeviceStore:
         clamped), a majority vote per voxel.  label_of: 256 entries, class -> label below n_labels, 255 = the class takes
         no part.  include_dyn=False: points with dyn == 1 take no part.
         Returns a dict of cuda tensors, each [nz, px, px], image rows: 'labels' uint8, the smallest label among the most
-        frequent ones (255: an empty voxel -- free or unseen is not decided, there is no ray casting); 'counts' and 'top'
+        frequent ones (255: an empty voxel -- free or unseen is not decided here: bev_voxel_rays); 'counts' and 'top'
         int32 holding the u32 numbers of labelled points and of points of the winning label.
         The store is not written: owed re-transforms are applied to what the call reads and stay owed.
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
@@ -714,6 +714,44 @@ class DeviceStore:
                                            counts.data_ptr(), top.data_ptr(), ctx.stream()))
         self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
         return {'labels': labels, 'counts': counts, 'top': top}
+
+    def bev_voxel_rays(self, prm, z_lo, z_step, nz, origins, first_frame=0, last_frame=None, include_dyn=False,
+                       max_points=None):
+        """One lidar ray per stored point of the live frames [first_frame, last_frame), cast through the voxel grid of
+        bev_voxel_labels (pca_bev_voxel_rays): from the sensor position of the point's frame to the point.  origins:
+        [frames, 3], a numpy array or a tensor, row i = the sensor position of frame first_frame + i in the store's current
+        coordinates (the pose track: it owes nothing); uploaded as f64.  The crop, the height filter and the class play no
+        part; include_dyn=False: points with dyn == 1 cast no ray.
+        Returns a dict of cuda tensors: 'seen' uint8 [nz, px, px], image rows, 1 = at least one ray passed through the voxel
+        (the end voxel of a ray is not marked by that ray); 'stats' int64 [4]: points considered, rays cast, rays dropped
+        for a coordinate that is not finite (or beyond 2^30), rays dropped for more than 16 384 voxel steps.
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        ctx, lib = self.ctx, self.ctx.lib
+        last_frame = self.n_frames if last_frame is None else last_frame
+        px = int(prm.px)
+        if isinstance(origins, torch.Tensor):
+            org = origins.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            org = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64)).to(self.device)
+        if org.dim() != 2 or org.shape[1] != 3 or org.shape[0] != last_frame - first_frame:
+            raise ValueError('origins must be [frames, 3], one row per frame of the range')
+        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
+        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+        bound = self.max_window_points()
+        max_points = bound if max_points is None else max(int(max_points), 1)
+        shape = (max(int(nz), 1), max(px, 1), max(px, 1))
+        seen = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(4, dtype=torch.int64, device=self.device)
+        if org.shape[0] == 0:
+            org = torch.zeros((1, 3), dtype=torch.float64, device=self.device)     # (never read: a valid pointer)
+        st = self.c_store()
+        ctx.check(lib.pca_bev_voxel_rays(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
+                                         self.head + last_frame, max_points, C.byref(prm), float(z_lo), float(z_step),
+                                         int(nz), 1 if include_dyn else 0, org.data_ptr(), pend_T, pend_ends, n_pend,
+                                         seen.data_ptr(), stats.data_ptr(), ctx.stream()))
+        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        return {'seen': seen, 'stats': stats}
 
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters

@@ -347,7 +347,7 @@ class SemanticPointCloudAccumulator:
         two present poses, no shift, zoom 1): the sample's grid with nz height bins over z_range metres, a majority vote
         over the labelled points of every voxel.  classes: a list of class lists, list i becomes label i; None: label =
         class for the classes 0 .. 31.  Returns DeviceStore.bev_voxel_labels' dict of cuda tensors 'labels', 'counts',
-        'top', each [nz, px, px]; labels 255 = no point in the voxel (free or unseen is not decided: no ray casting).
+        'top', each [nz, px, px]; labels 255 = no point in the voxel (free or unseen is not decided here: voxel_occupancy).
         Nothing is written: the store, the owed re-transforms and every later sample stay as they are."""
         if part not in ('present', 'future', 'full'):
             raise ValueError("part must be 'present', 'future' or 'full'")
@@ -357,6 +357,37 @@ class SemanticPointCloudAccumulator:
         rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
         return gen.voxel_labels_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, classes=classes,
                                        include_dyn=include_dyn)
+
+    def voxel_occupancy(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False,
+                        origins=None):
+        """Extension (no reference counterpart): voxel_labels of `part` plus what the lidar rays tell about its empty voxels,
+        in the same un-augmented frame.  One ray per stored point of the part, from the sensor position of the point's frame
+        to the point (DeviceStore.bev_voxel_rays).  origins: [frames of the part, 3] sensor positions in the store's
+        coordinates; None: the pose-track rows of the part's frames (a caller whose sensor does not sit at the pose passes
+        its own, e.g. NuScenes with the lidar above the ego origin).  One origin per stored frame -- the merged sweeps of a
+        NuScenes sample share their key frame's -- and no per-beam minimum or maximum range.
+        Returns cuda tensors: 'labels', 'counts', 'top' as voxel_labels gives them; 'seen' uint8 [nz, px, px], 'stats'
+        int64 [4]; 'state' uint8 [nz, px, px]: 2 = occupied (counts > 0), else 1 = free (a ray passed through), else
+        0 = unseen (what semantic-scene-completion training has to ignore).  Nothing is written to the store."""
+        import torch
+        if part not in ('present', 'future', 'full'):
+            raise ValueError("part must be 'present', 'future' or 'full'")
+        gen = self.sem_bev_generator
+        self.store.poll_status()
+        pcs, trajs = self._window_inputs_for(present_idx, True)
+        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
+        pc = pcs['pc_' + part]
+        if origins is None:
+            w = pc.window
+            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[part]
+            if w.future_is_present:
+                f0, f1 = w.first, w.last
+            origins = self._track.as_array()[f0:f1]
+        out = gen.voxel_labels_device(pc, rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, classes=classes,
+                                      include_dyn=include_dyn)
+        out.update(gen.voxel_rays_device(pc, origins, rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, include_dyn=include_dyn))
+        out['state'] = torch.where(out['counts'] != 0, 2, out['seen'].to(torch.int32)).to(torch.uint8)
+        return out
 
     def generate_bev_many(self, present_idxs, gen_future: bool = True):
         """Extension (no reference counterpart): the samples generate_bev(idx, 1, gen_future)[0] would return for every idx of
