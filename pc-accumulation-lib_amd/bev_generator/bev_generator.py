@@ -47,13 +47,17 @@ class WindowPart:
         self.window = window
         self.name = name
 
+    def frames(self):
+        """(lo, hi): the part is the live frames [lo, hi) of the window's store.  The only place that knows it."""
+        w = self.window
+        lo, hi = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[self.name]
+        return (w.first, w.last) if w.future_is_present else (lo, hi)
+
     def to_numpy(self):
         """Materialises the reference's host array (concatenated frames minus the origin)."""
         w = self.window
         rows = w.store.frame_rows()
-        lo, hi = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[self.name]
-        if w.future_is_present:
-            lo, hi = w.first, w.last
+        lo, hi = self.frames()
         out = np.concatenate(rows[lo:hi]) if hi > lo else np.zeros((0, 10))
         out[:, :3] = out[:, :3] - w.origin
         return out

@@ -238,16 +238,40 @@ class SemBEVGenerator(BEVGenerator):
                 raise ValueError(f"sem_planes: '{name}' is the name of one of the sample's own planes")
         return list(planes), [self._classes_of(v) for v in planes.values()]
 
+    # ---- one point set, one read-only pass: what class_planes_device, elev_partition_device, voxel_labels_device and
+    #      voxel_rays_device share (a new pass of this family plugs in here and in DeviceStore._window_pass) ----
+    def _pass_params(self, pc, rot_mat, dx, dy, aug_view_size):
+        """pca_bev_params of a pass over `pc`: a WindowPart brings its window's origin, host rows are in BEV-frame metres."""
+        if isinstance(pc, WindowPart):
+            return self._raster_params(pc.window.origin, rot_mat, dx, dy, aug_view_size, pc.window.store.intensity_div255)
+        return self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
+
+    def _one_set_pass(self, pc, key, rot_mat, dx, dy, aug_view_size, per_frame=False):
+        """(store, prm, frame range) a pass over one point set is called with: the window's store and the part's frames, or
+        -- host rows: one array, per_frame: a list of arrays -- the temporary store `key` loaded with them, all of it."""
+        prm = self._pass_params(pc, rot_mat, dx, dy, aug_view_size)
+        if isinstance(pc, WindowPart):
+            lo, hi = pc.frames()
+            return pc.window.store, prm, dict(first_frame=lo, last_frame=hi)
+        st = self._tmp_store(key)
+        st.load_rows(pc if per_frame else [pc])
+        return st, prm, {}
+
+    @staticmethod
+    def _voxel_grid(z_range, nz):
+        """(z_lo, z_step, nz) of nz height bins over z_range = (lo, hi); nz <= 0 gives a NaN step, which the C call refuses."""
+        lo, hi, nz = float(z_range[0]), float(z_range[1]), int(nz)
+        return lo, ((hi - lo) / nz if nz > 0 else float('nan')), nz
+
     def class_planes_device(self, pc_present, pc_future, pc_full, groups, rot_mat, dx, dy, aug_view_size, want_counts=False):
         """(prob_f16, prob_f64, counts | None), cuda [3, len(groups) (+ 1), px, px]: the planes of the class groups over the
         static points of the three sets, in the frame the 21 planes are rasterised in (DeviceStore.bev_class_planes)."""
+        prm = self._pass_params(pc_present, rot_mat, dx, dy, aug_view_size)
         if isinstance(pc_present, WindowPart):
             w = pc_present.window
-            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
             return w.store.bev_class_planes(w.split, prm, groups, first_frame=w.first, last_frame=w.last,
                                             want_counts=want_counts)
         # host arrays go through the temporary stores, as in rasterise: 'full' is an input of its own
-        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
         st = self._tmp_store('pf')
         st.load_rows([pc_present, pc_future])
         a = st.bev_class_planes(1, prm, groups, want_counts=want_counts)
@@ -303,20 +327,10 @@ class SemBEVGenerator(BEVGenerator):
         (DeviceStore.bev_elev_partition: the dict of cuda tensors 'elev', 'observed', 'flags', 'counts').  pc: a WindowPart
         (flags in the order of the part's frames in the store) or host rows in BEV-frame metres (flags in row order).
         mark_dyn applies to a WindowPart only: the elevated points of the device window get dyn = 1, for good."""
-        if isinstance(pc, WindowPart):
-            w = pc.window
-            lo, hi = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
-            if w.future_is_present:
-                lo, hi = w.first, w.last
-            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
-            return w.store.bev_elev_partition(prm, elev_thresh, first_frame=lo, last_frame=hi, include_dyn=include_dyn,
-                                              mark_dyn=mark_dyn)
-        if mark_dyn:
+        if mark_dyn and not isinstance(pc, WindowPart):
             raise ValueError('mark_dyn needs a device window: host rows are not written')
-        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
-        st = self._tmp_store('elev')
-        st.load_rows([pc])
-        return st.bev_elev_partition(prm, elev_thresh, include_dyn=include_dyn)
+        st, prm, frames = self._one_set_pass(pc, 'elev', rot_mat, dx, dy, aug_view_size)
+        return st.bev_elev_partition(prm, elev_thresh, include_dyn=include_dyn, mark_dyn=mark_dyn, **frames)
 
     # ---- semantic occupancy labels (extension: pca_bev_voxel_labels) -------------------------------
     @staticmethod
@@ -344,24 +358,12 @@ class SemBEVGenerator(BEVGenerator):
         height bins over z_range = (lo, hi) metres of that frame (DeviceStore.bev_voxel_labels: the dict of cuda tensors
         'labels', 'counts', 'top', each [nz, px, px]).  pc: a WindowPart or host rows in BEV-frame metres.  classes: see
         voxel_label_table (sem_idxs names are taken too)."""
-        lo, hi = float(z_range[0]), float(z_range[1])
-        nz = int(nz)
-        z_step = (hi - lo) / nz if nz > 0 else float('nan')
+        grid = self._voxel_grid(z_range, nz)
         if classes is not None:
             classes = [self._classes_of(g) for g in classes]
         table, n_labels = self.voxel_label_table(classes)
-        if isinstance(pc, WindowPart):
-            w = pc.window
-            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
-            if w.future_is_present:
-                f0, f1 = w.first, w.last
-            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
-            return w.store.bev_voxel_labels(prm, lo, z_step, nz, table, n_labels, first_frame=f0, last_frame=f1,
-                                            include_dyn=include_dyn)
-        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
-        st = self._tmp_store('voxel')
-        st.load_rows([pc])
-        return st.bev_voxel_labels(prm, lo, z_step, nz, table, n_labels, include_dyn=include_dyn)
+        st, prm, frames = self._one_set_pass(pc, 'voxel', rot_mat, dx, dy, aug_view_size)
+        return st.bev_voxel_labels(prm, *grid, table, n_labels, include_dyn=include_dyn, **frames)
 
     # ---- rays through the voxel grid: free against unseen (extension: pca_bev_voxel_rays) ------------
     def voxel_rays_device(self, pc, origins, rot_mat, dx, dy, aug_view_size, z_range, nz, include_dyn=False):
@@ -370,23 +372,13 @@ class SemBEVGenerator(BEVGenerator):
         (uint8 [nz, px, px], 1 = a ray passed through) and 'stats' (int64 [4]).  pc: a WindowPart, with `origins`
         [frames, 3] the sensor positions of exactly that part's frames in the store's coordinates; or a list of per-frame
         host row arrays in BEV-frame metres, with one origin each in the same frame."""
-        lo, hi = float(z_range[0]), float(z_range[1])
-        nz = int(nz)
-        z_step = (hi - lo) / nz if nz > 0 else float('nan')
-        if isinstance(pc, WindowPart):
-            w = pc.window
-            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[pc.name]
-            if w.future_is_present:
-                f0, f1 = w.first, w.last
-            prm = self._raster_params(w.origin, rot_mat, dx, dy, aug_view_size, w.store.intensity_div255)
-            return w.store.bev_voxel_rays(prm, lo, z_step, nz, origins, first_frame=f0, last_frame=f1, include_dyn=include_dyn)
+        grid = self._voxel_grid(z_range, nz)
         if isinstance(pc, np.ndarray):
             raise ValueError('voxel_rays_device: host rows come as a list of per-frame arrays, one origin each')
-        frames = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in pc]
-        prm = self._raster_params(np.zeros(3), rot_mat, dx, dy, aug_view_size, False)
-        st = self._tmp_store('rays')
-        st.load_rows(frames)
-        return st.bev_voxel_rays(prm, lo, z_step, nz, origins, include_dyn=include_dyn)
+        if not isinstance(pc, WindowPart):
+            pc = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in pc]
+        st, prm, frames = self._one_set_pass(pc, 'rays', rot_mat, dx, dy, aug_view_size, per_frame=True)
+        return st.bev_voxel_rays(prm, *grid, origins, include_dyn=include_dyn, **frames)
 
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the

@@ -111,6 +111,7 @@ __global__ __launch_bounds__(CC_THREADS) void bev_class_cells(const ClsArgs a)
 // ---------------------------------------------------------------------------------------------
 // the workspace: the uint16_t records, then the table (side_layout)
 static SideLayout cls_layout(int64_t max_points, int px) { return side_layout(max_points, px, 2, 0, "PCA_BEV_CLASS_G"); }
+static const WindowPass CLS_PASS = {"bev class planes", true, true};
 
 extern "C" {
 
@@ -126,24 +127,13 @@ int pca_bev_class_planes(pca_ctx *ctx, const pca_store *store, const int64_t *fr
     if (max_points < 1) max_points = 1;
     hipStream_t s = (hipStream_t)stream;
     // every check comes before the first launch (a noted K1 included)
-    if (!store || !frame_off || !prm || !groups || !workspace || (!prob && !prob_f16 && !counts)) {
-        ctx->err = "bev class planes: bad arguments";
-        return -1;
-    }
-    if (!store->x || !store->y || !store->z || !store->rgbs || !store->dyn) {
-        ctx->err = "bev class planes: the store's x, y, z, rgbs and dyn arrays are needed";
-        return -1;
-    }
-    if (n_groups < 1 || n_groups > PCA_BEV_MAX_CLASS_GROUPS) { ctx->err = "bev class planes: n_groups must be in 1..16"; return -1; }
-    if (!(slot_begin <= slot_split && slot_split <= slot_end)) {
-        ctx->err = "bev class planes: need slot_begin <= slot_split <= slot_end";
-        return -1;
-    }
     ClsArgs A;
     char *w;
-    if (side_check(ctx, "bev class planes", store, frame_off, slot_begin, slot_split, slot_end, max_points, prm, pending_Ts,
-                   pending_slot_ends, n_pending, workspace, workspace_bytes, cls_layout(max_points, prm->px), A.s, w))
+    if (window_check(ctx, CLS_PASS, groups && workspace && (prob || prob_f16 || counts), store, frame_off, slot_begin, slot_split,
+                     slot_end, max_points, prm, pending_Ts, pending_slot_ends, n_pending, A.s))
         return -1;
+    if (n_groups < 1 || n_groups > PCA_BEV_MAX_CLASS_GROUPS) { ctx->err = "bev class planes: n_groups must be in 1..16"; return -1; }
+    if (side_tiles(ctx, CLS_PASS.what, slot_split, workspace, workspace_bytes, cls_layout(max_points, prm->px), A.s, w)) return -1;
     A.n_groups = n_groups;
     A.recs = reinterpret_cast<uint16_t *>(w);
     A.prob = prob; A.prob_f16 = prob_f16; A.counts = counts;
@@ -152,12 +142,8 @@ int pca_bev_class_planes(pca_ctx *ctx, const pca_store *store, const int64_t *fr
         for (int g = 0; g < n_groups; ++g) bits |= (uint32_t)((groups[g].mask[c >> 6] >> (c & 63)) & 1ull) << g;
         A.cls_bits[c] = bits;
     }
-    PCA_CHECK(ctx, hipSetDevice(ctx->device));
-    if (pca_k1_flush_pending(ctx)) return -1;               // a noted K1 runs on its own first, as before a banded raster
-    if (side_grant_lds<bev_class_bin>(ctx)) return -1;
     const ClsArgs &args = A;
-    if (args.s.G > 0)
-        PCA_LAUNCH_SHM(ctx, PCA_K_BEV_CLASS_BIN, bev_class_bin, dim3(args.s.G), dim3(SIDE_BIN_THREADS), (size_t)args.s.T * 4, s, args);
+    if (side_launch_bin<bev_class_bin>(ctx, PCA_K_BEV_CLASS_BIN, args, s)) return -1;
     PCA_LAUNCH(ctx, PCA_K_BEV_CLASS_CELLS, bev_class_cells, dim3(args.s.T), dim3(CC_THREADS), s, args);
     PCA_CHECK(ctx, hipGetLastError());
     return 0;

@@ -157,6 +157,7 @@ __global__ __launch_bounds__(ET_THREADS) void bev_elev_totals(const ElvArgs a)
 // ---------------------------------------------------------------------------------------------
 // the workspace: the records, then the table, then the per-tile totals (side_layout: `tail`)
 static SideLayout elv_layout(int64_t max_points, int px) { return side_layout(max_points, px, sizeof(ElvRec), 3 * 8, "PCA_BEV_ELEV_G"); }
+static const WindowPass ELV_PASS = {"bev elev partition", false, false};
 
 extern "C" {
 
@@ -172,33 +173,21 @@ int pca_bev_elev_partition(pca_ctx *ctx, const pca_store *store, const int64_t *
     if (max_points < 1) max_points = 1;
     hipStream_t s = (hipStream_t)stream;
     // every check comes before the first launch (a noted K1 included)
-    if (!store || !frame_off || !prm || !workspace || (!elev && !observed && !flags && !counts)) {
-        ctx->err = "bev elev partition: bad arguments";
-        return -1;
-    }
-    if (!store->x || !store->y || !store->z || !store->dyn) {
-        ctx->err = "bev elev partition: the store's x, y, z and dyn arrays are needed";
-        return -1;
-    }
-    if (elev_thresh != elev_thresh) { ctx->err = "bev elev partition: elev_thresh is NaN"; return -1; }
-    if (slot_begin > slot_end) { ctx->err = "bev elev partition: need slot_begin <= slot_end"; return -1; }
     ElvArgs A;
-    const SideLayout l = elv_layout(max_points, prm->px);
     char *w;
-    if (side_check(ctx, "bev elev partition", store, frame_off, slot_begin, slot_begin, slot_end, max_points, prm, pending_Ts,
-                   pending_slot_ends, n_pending, workspace, workspace_bytes, l, A.s, w))
+    if (window_check(ctx, ELV_PASS, workspace && (elev || observed || flags || counts), store, frame_off, slot_begin, slot_begin,
+                     slot_end, max_points, prm, pending_Ts, pending_slot_ends, n_pending, A.s))
         return -1;
+    if (elev_thresh != elev_thresh) { ctx->err = "bev elev partition: elev_thresh is NaN"; return -1; }
+    const SideLayout l = elv_layout(max_points, prm->px);
+    if (side_tiles(ctx, ELV_PASS.what, slot_begin, workspace, workspace_bytes, l, A.s, w)) return -1;
     A.thresh = elev_thresh;
     A.include_dyn = include_dyn;
     A.recs = reinterpret_cast<ElvRec *>(w);
     A.tile_counts = reinterpret_cast<int64_t *>(w + l.tail);
     A.elev = elev; A.observed = observed; A.flags = flags; A.counts = counts;
-    PCA_CHECK(ctx, hipSetDevice(ctx->device));
-    if (pca_k1_flush_pending(ctx)) return -1;               // a noted K1 runs on its own first, as before the class planes
-    if (side_grant_lds<bev_elev_bin>(ctx)) return -1;
     const ElvArgs &args = A;
-    if (args.s.G > 0)
-        PCA_LAUNCH_SHM(ctx, PCA_K_BEV_ELEV_BIN, bev_elev_bin, dim3(args.s.G), dim3(SIDE_BIN_THREADS), (size_t)args.s.T * 4, s, args);
+    if (side_launch_bin<bev_elev_bin>(ctx, PCA_K_BEV_ELEV_BIN, args, s)) return -1;
     PCA_LAUNCH(ctx, PCA_K_BEV_ELEV_CELLS, bev_elev_cells, dim3(args.s.T), dim3(EC_THREADS), s, args);
     if (args.counts) PCA_LAUNCH(ctx, PCA_K_BEV_ELEV_CELLS, bev_elev_totals, dim3(1), dim3(ET_THREADS), s, args);
     PCA_CHECK(ctx, hipGetLastError());

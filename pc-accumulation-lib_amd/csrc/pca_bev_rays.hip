@@ -162,6 +162,8 @@ __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
     if (tid < 4 && a.stats && s_stat[tid]) atomicAdd(a.stats + tid, s_stat[tid]);
 }
 
+static const WindowPass RAY_PASS = {"bev voxel rays", false, false};
+
 extern "C" {
 
 int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off, int slot_begin, int slot_end,
@@ -173,27 +175,11 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
     if (max_points < 1) max_points = 1;
     hipStream_t s = (hipStream_t)stream;
     // every check comes before the first launch (a noted K1 and the clearing of the outputs included)
-    if (!store || !frame_off || !prm || !origins || (!seen && !stats)) {
-        ctx->err = "bev voxel rays: bad arguments";
-        return -1;
-    }
-    if (!store->x || !store->y || !store->z || !store->dyn) {
-        ctx->err = "bev voxel rays: the store's x, y, z and dyn arrays are needed";
-        return -1;
-    }
-    if (prm->px < 1 || prm->px > 1024) { ctx->err = "bev voxel rays: px must be in 1..1024"; return -1; }
-    if (nz < 1 || nz > PCA_BEV_VOXEL_MAX_Z) { ctx->err = "bev voxel rays: nz must be in 1..32"; return -1; }
-    if (!(fabs(z_lo) < __builtin_huge_val())) { ctx->err = "bev voxel rays: z_lo must be finite"; return -1; }
-    if (!(z_step > 0.0 && z_step < __builtin_huge_val())) { ctx->err = "bev voxel rays: z_step must be finite and > 0"; return -1; }
-    if (bev_check_rotation(ctx, "bev voxel rays", prm)) return -1;
-    if (slot_begin > slot_end) { ctx->err = "bev voxel rays: need slot_begin <= slot_end"; return -1; }
     RayArgs A;
-    if (bev_fill_owed(ctx, "bev voxel rays", pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, A.owed)) return -1;
-    A.st = *store;
-    A.frame_off = frame_off;
-    A.slot_begin = slot_begin; A.slot_end = slot_end;
-    A.max_points = max_points;
-    A.prm = *prm;
+    if (window_check(ctx, RAY_PASS, origins && (seen || stats), store, frame_off, slot_begin, slot_begin, slot_end, max_points, prm,
+                     pending_Ts, pending_slot_ends, n_pending, A))
+        return -1;
+    if (voxel_grid_check(ctx, RAY_PASS.what, z_lo, z_step, nz)) return -1;
     A.z_lo = z_lo; A.z_step = z_step;
     A.nz = nz; A.include_dyn = include_dyn;
     const int64_t chunks = (max_points + RAY_THREADS - 1) / RAY_THREADS;
@@ -203,7 +189,6 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
     A.origins = origins;
     A.seen = seen;
     A.stats = reinterpret_cast<unsigned long long *>(stats);
-    A.status = ctx->ticket + 1;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     if (pca_k1_flush_pending(ctx)) return -1;               // a noted K1 runs on its own first, as before the occupancy labels
     if (seen) PCA_CHECK(ctx, hipMemsetAsync(seen, 0, (size_t)nz * prm->px * prm->px, s));

@@ -19,7 +19,6 @@
 #define SIDE_CHUNK 8192           // points per workgroup of level 1 the launch is sized for
 #define SIDE_CELLS_THREADS 256    // workgroup size of level 2
 #define SIDE_PLACES (SIDE_MAX_G + 8)   // places of a table row at most
-#define SIDE_PX_MAX 1024
 
 struct SideArgs {                 // the first member of every pass's argument block
     pca_store st;
@@ -219,31 +218,21 @@ static inline SideLayout side_layout(int64_t max_points, int px, int64_t record_
     l.total = l.tail + pca_align256((int64_t)l.T * tile_bytes) + 512;
     return l;
 }
-// The checks the entry points share (each has checked its own pointers and slot order) and the common argument block;
-// l: the pass's layout for (max_points, prm->px); `base`: the 256-byte aligned workspace its offsets count from.
-static inline int side_check(pca_ctx *ctx, const char *what, const pca_store *store, const int64_t *frame_off, int slot_begin,
-                             int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm, const double *pending_Ts,
-                             const int *pending_slot_ends, int n_pending, void *workspace, int64_t workspace_bytes,
+// The tiled passes' part of the checks, after window_check (pca_bev_view.h) has filled A's window: the tiles, the table and
+// the workspace; l: the pass's layout for (A.max_points, A.prm.px); `base`: the 256-byte aligned workspace its offsets count from.
+static inline int side_tiles(pca_ctx *ctx, const char *what, int slot_split, void *workspace, int64_t workspace_bytes,
                              const SideLayout &l, SideArgs &A, char *&base)
 {
     const std::string w(what);
-    if (prm->px < 1 || prm->px > SIDE_PX_MAX) { ctx->err = w + ": px must be in 1..1024"; return -1; }
-    if (bev_check_rotation(ctx, what, prm)) return -1;
-    if (max_points >= (1ll << 32) - 2 * SIDE_BIN_THREADS) { ctx->err = w + ": window too large for 32-bit positions"; return -1; }
+    if (A.max_points >= (1ll << 32) - 2 * SIDE_BIN_THREADS) { ctx->err = w + ": window too large for 32-bit positions"; return -1; }
     if (workspace_bytes < l.total) { ctx->err = w + ": workspace too small"; return -1; }
-    if (bev_fill_owed(ctx, what, pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, A.owed)) return -1;
-    A.st = *store;
-    A.frame_off = frame_off;
-    A.slot_begin = slot_begin; A.slot_split = slot_split; A.slot_end = slot_end;
-    A.max_points = max_points;
-    A.prm = *prm;
-    A.tx = side_tiles_x(prm->px);
+    A.slot_split = slot_split;
+    A.tx = side_tiles_x(A.prm.px);
     A.T = l.T;
-    A.G = slot_end > slot_begin ? l.G : 0;                  // a window without a slot: no launch over zero points
+    A.G = A.slot_end > A.slot_begin ? l.G : 0;              // a window without a slot: no launch over zero points
     A.Gr = l.Gr; A.Gp = l.Gp;
     base = reinterpret_cast<char *>(pca_align256(reinterpret_cast<intptr_t>(workspace)));
     A.table = reinterpret_cast<uint2 *>(base + l.table);
-    A.status = ctx->ticket + 1;
     return 0;
 }
 // level 1's histogram is 64 KiB of dynamic LDS at 1024^2: asked for once per process and kernel
@@ -255,5 +244,17 @@ static int side_grant_lds(pca_ctx *ctx)
     PCA_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (SIDE_PX_MAX / TS) * (SIDE_PX_MAX / TS) * 4));
     lds_set = true;
+    return 0;
+}
+// The launch tail the tiled passes share: the device, a noted K1 on its own first (as before a banded raster), level 1's LDS
+// and level 1 itself -- unless the window holds no slot.  Args: the pass's argument block, SideArgs first.
+template <auto BIN, typename Args>
+static int side_launch_bin(pca_ctx *ctx, int kernel_id, const Args &args, hipStream_t s)
+{
+    PCA_CHECK(ctx, hipSetDevice(ctx->device));
+    if (pca_k1_flush_pending(ctx)) return -1;
+    if (side_grant_lds<BIN>(ctx)) return -1;
+    if (args.s.G > 0)
+        PCA_LAUNCH_SHM(ctx, kernel_id, BIN, dim3(args.s.G), dim3(SIDE_BIN_THREADS), (size_t)args.s.T * 4, s, args);
     return 0;
 }

@@ -113,8 +113,8 @@ __device__ __forceinline__ int bev_table_group(int Gp, int p)
     return (p - x * Gp) * 8 + x;                            // may be >= G: an unused place of the row
 }
 
-// ---- host side: the argument checks the three entry points share.  `what` is the message prefix ("bev", "bev class planes",
-// "bev elev partition"); on failure ctx->err is set and -1 returned. ----
+// ---- host side: the argument checks the entry points share.  `what` is the message prefix ("bev", "bev class planes",
+// "bev elev partition", ...); on failure ctx->err is set and -1 returned. ----
 // the elevation is min(z - origin_z) and the cell function drops R's third row and column: the rotation has to leave z alone
 // (rotation_matrix_3d of the reference)
 static inline int bev_check_rotation(pca_ctx *ctx, const char *what, const pca_bev_params *prm)
@@ -143,5 +143,49 @@ static inline int bev_fill_owed(pca_ctx *ctx, const char *what, const double *pe
         o.pend_slot_end[k] = pending_slot_ends[k];
         for (int i = 0; i < 12; ++i) o.pend_T[k].m[i] = pending_Ts[16 * k + i];
     }
+    return 0;
+}
+
+// ---- host side: a read-only pass over a window of the store (the class planes, the elevation partition, the occupancy labels,
+// the rays through the voxel grid; the next pass of the family starts here).  The main raster has its own checks. ----
+#define SIDE_PX_MAX 1024          // the largest grid of these passes (no banding)
+// what: the message prefix; rgbs: the pass reads the class byte; split: its window has a slot_split
+struct WindowPass { const char *what; bool rgbs, split; };
+// The checks every entry point shares, before anything is launched: the pointers (own_ok: those of the pass's own arguments),
+// the store's arrays, the slot order, px, the rotation, the owed chain -- and the fields every argument block has (Args:
+// SideArgs or RayArgs; a pass without a split hands slot_begin in its place).
+template <typename Args>
+static inline int window_check(pca_ctx *ctx, const WindowPass &pass, bool own_ok, const pca_store *store, const int64_t *frame_off,
+                               int slot_begin, int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm,
+                               const double *pending_Ts, const int *pending_slot_ends, int n_pending, Args &A)
+{
+    const std::string w(pass.what);
+    if (!store || !frame_off || !prm || !own_ok) { ctx->err = w + ": bad arguments"; return -1; }
+    if (!store->x || !store->y || !store->z || (pass.rgbs && !store->rgbs) || !store->dyn) {
+        ctx->err = w + ": the store's x, y, z" + (pass.rgbs ? ", rgbs" : "") + " and dyn arrays are needed";
+        return -1;
+    }
+    if (!(slot_begin <= slot_split && slot_split <= slot_end)) {
+        ctx->err = w + (pass.split ? ": need slot_begin <= slot_split <= slot_end" : ": need slot_begin <= slot_end");
+        return -1;
+    }
+    if (prm->px < 1 || prm->px > SIDE_PX_MAX) { ctx->err = w + ": px must be in 1..1024"; return -1; }
+    if (bev_check_rotation(ctx, pass.what, prm)) return -1;
+    if (bev_fill_owed(ctx, pass.what, pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, A.owed)) return -1;
+    A.st = *store;
+    A.frame_off = frame_off;
+    A.slot_begin = slot_begin; A.slot_end = slot_end;
+    A.max_points = max_points;
+    A.prm = *prm;
+    A.status = ctx->ticket + 1;
+    return 0;
+}
+// the voxel grid of the occupancy labels and of the rays: nz height bins of z_step from z_lo
+static inline int voxel_grid_check(pca_ctx *ctx, const char *what, double z_lo, double z_step, int nz)
+{
+    const std::string w(what);
+    if (nz < 1 || nz > PCA_BEV_VOXEL_MAX_Z) { ctx->err = w + ": nz must be in 1..32"; return -1; }
+    if (!(fabs(z_lo) < __builtin_huge_val())) { ctx->err = w + ": z_lo must be finite"; return -1; }
+    if (!(z_step > 0.0 && z_step < __builtin_huge_val())) { ctx->err = w + ": z_step must be finite and > 0"; return -1; }
     return 0;
 }

@@ -137,6 +137,7 @@ __global__ __launch_bounds__(VC_THREADS) void bev_voxel_cells(const VoxArgs a)
 // ---------------------------------------------------------------------------------------------
 // the workspace: the uint16_t records, then the table (side_layout)
 static SideLayout vox_layout(int64_t max_points, int px) { return side_layout(max_points, px, 2, 0, "PCA_BEV_VOXEL_G"); }
+static const WindowPass VOX_PASS = {"bev voxel labels", true, false};
 
 extern "C" {
 
@@ -152,29 +153,19 @@ int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *fr
     if (max_points < 1) max_points = 1;
     hipStream_t s = (hipStream_t)stream;
     // every check comes before the first launch (a noted K1 included)
-    if (!store || !frame_off || !prm || !label_of || !workspace || (!labels && !counts && !top)) {
-        ctx->err = "bev voxel labels: bad arguments";
+    VoxArgs A;
+    char *w;
+    if (window_check(ctx, VOX_PASS, label_of && workspace && (labels || counts || top), store, frame_off, slot_begin, slot_begin,
+                     slot_end, max_points, prm, pending_Ts, pending_slot_ends, n_pending, A.s))
         return -1;
-    }
-    if (!store->x || !store->y || !store->z || !store->rgbs || !store->dyn) {
-        ctx->err = "bev voxel labels: the store's x, y, z, rgbs and dyn arrays are needed";
-        return -1;
-    }
-    if (nz < 1 || nz > PCA_BEV_VOXEL_MAX_Z) { ctx->err = "bev voxel labels: nz must be in 1..32"; return -1; }
+    if (voxel_grid_check(ctx, VOX_PASS.what, z_lo, z_step, nz)) return -1;
     if (n_labels < 1 || n_labels > PCA_BEV_VOXEL_MAX_LABELS) { ctx->err = "bev voxel labels: n_labels must be in 1..32"; return -1; }
-    if (!(fabs(z_lo) < __builtin_huge_val())) { ctx->err = "bev voxel labels: z_lo must be finite"; return -1; }
-    if (!(z_step > 0.0 && z_step < __builtin_huge_val())) { ctx->err = "bev voxel labels: z_step must be finite and > 0"; return -1; }
     for (int c = 0; c < 256; ++c)
         if (label_of[c] != 255 && label_of[c] >= n_labels) {
             ctx->err = "bev voxel labels: label_of[" + std::to_string(c) + "] must be below n_labels, or 255";
             return -1;
         }
-    if (slot_begin > slot_end) { ctx->err = "bev voxel labels: need slot_begin <= slot_end"; return -1; }
-    VoxArgs A;
-    char *w;
-    if (side_check(ctx, "bev voxel labels", store, frame_off, slot_begin, slot_begin, slot_end, max_points, prm, pending_Ts,
-                   pending_slot_ends, n_pending, workspace, workspace_bytes, vox_layout(max_points, prm->px), A.s, w))
-        return -1;
+    if (side_tiles(ctx, VOX_PASS.what, slot_begin, workspace, workspace_bytes, vox_layout(max_points, prm->px), A.s, w)) return -1;
     A.z_lo = z_lo; A.z_step = z_step;
     A.nz = nz; A.n_labels = n_labels; A.include_dyn = include_dyn;
     // the slabs of level 2: as few as the counters allow, then of equal height
@@ -184,12 +175,8 @@ int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *fr
     A.recs = reinterpret_cast<uint16_t *>(w);
     A.labels = labels; A.counts = counts; A.top = top;
     for (int c = 0; c < 256; ++c) A.label_of[c] = label_of[c];
-    PCA_CHECK(ctx, hipSetDevice(ctx->device));
-    if (pca_k1_flush_pending(ctx)) return -1;               // a noted K1 runs on its own first, as before the class planes
-    if (side_grant_lds<bev_voxel_bin>(ctx)) return -1;
     const VoxArgs &args = A;
-    if (args.s.G > 0)
-        PCA_LAUNCH_SHM(ctx, PCA_K_BEV_VOXEL_BIN, bev_voxel_bin, dim3(args.s.G), dim3(SIDE_BIN_THREADS), (size_t)args.s.T * 4, s, args);
+    if (side_launch_bin<bev_voxel_bin>(ctx, PCA_K_BEV_VOXEL_BIN, args, s)) return -1;
     PCA_LAUNCH_SHM(ctx, PCA_K_BEV_VOXEL_CELLS, bev_voxel_cells, dim3(args.s.T), dim3(VC_THREADS),
                    (size_t)args.zs * n_labels * TCELLS * 4, s, args);
     PCA_CHECK(ctx, hipGetLastError());

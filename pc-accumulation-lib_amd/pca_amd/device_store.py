@@ -607,6 +607,30 @@ class DeviceStore:
             ws[0] = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
         return ws[0]
 
+    def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None):
+        """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
+        bev_elev_partition, bev_voxel_labels, bev_voxel_rays; the next pass of the family starts here): last_frame's default,
+        the bound at which the window is cut (max_points; default: the live window's own) and -- side = (name,
+        pca_*_workspace_bytes) -- the pass's scratch.  Returns (last_frame, max_points, call).
+        call(fn, own, outs, split_frame=None) is the one C call
+            fn(ctx, store, frame_off, slots, max_points, prm, *own, owed chain, [workspace], *outs' pointers, stream)
+        with the owed chain taken read-only from bev_pending (which flushes it when the window does not cover what is owed).
+        The C call runs a noted K1 first: after it nothing is noted any more; a refused call raises and leaves it noted."""
+        last_frame = self.n_frames if last_frame is None else last_frame
+        max_points = self.max_window_points() if max_points is None else max(int(max_points), 1)
+        ws = None if side is None else self._side_workspace(*side, max_points, int(prm.px))
+
+        def call(fn, own, outs, split_frame=None):
+            ctx = self.ctx
+            n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+            slots = [self.head + f for f in (first_frame, split_frame, last_frame) if f is not None]
+            st = self.c_store()
+            ctx.check(fn(ctx.h, C.byref(st), self.frame_off.data_ptr(), *slots, max_points, C.byref(prm), *own, pend_T, pend_ends,
+                         n_pend, *(() if ws is None else (ws.data_ptr(), ws.numel())),
+                         *(None if t is None else t.data_ptr() for t in outs), ctx.stream()))
+            self._k1_noted = None
+        return last_frame, max_points, call
+
     def bev_class_planes(self, split_frame, prm, groups, first_frame=0, last_frame=None, want_counts=False):
         """Planes of any semantic class groups over live frames [first_frame, last_frame), 'present' = frames before
         split_frame (pca_bev_class_planes: one counts-only pass for all groups).  groups: a list of class-index lists (1..16
@@ -614,27 +638,17 @@ class DeviceStore:
         float16 / float64 and -- want_counts -- [3, len(groups) + 1, px, px] int32 holding the u32 counts per group, the last
         slot every static point; set order {present, future, full}.  The store is not written: owed re-transforms are applied
         to what the call reads and stay owed."""
-        ctx, lib = self.ctx, self.ctx.lib
-        self.flush_k1()
-        last_frame = self.n_frames if last_frame is None else last_frame
+        lib = self.ctx.lib
         px, ng = int(prm.px), len(groups)
         cg = (_lib.PcaClassGroup * max(ng, 1))()
         for k, g in enumerate(groups):
             cg[k].mask[:] = list(_lib.class_mask(g))
-        # the owed chain, read only (bev_pending flushes it when this raster does not cover what is owed)
-        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
-        max_points = self.max_window_points()
-        ws = self._side_workspace('class', lib.pca_bev_class_workspace_bytes, max_points, px)
+        _, _, call = self._window_pass(prm, first_frame, last_frame, side=('class', lib.pca_bev_class_workspace_bytes))
         shape = (3, max(ng, 1), max(px, 1), max(px, 1))
         p16 = torch.empty(shape, dtype=torch.float16, device=self.device)
         p64 = torch.empty(shape, dtype=torch.float64, device=self.device)
         cnt = torch.empty((3, shape[1] + 1) + shape[2:], dtype=torch.int32, device=self.device) if want_counts else None
-        st = self.c_store()
-        ctx.check(lib.pca_bev_class_planes(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
-                                           self.head + split_frame, self.head + last_frame, max_points, C.byref(prm), cg, ng,
-                                           pend_T, pend_ends, n_pend, ws.data_ptr(), ws.numel(),
-                                           p64.data_ptr(), p16.data_ptr(), None if cnt is None else cnt.data_ptr(),
-                                           ctx.stream()))
+        call(lib.pca_bev_class_planes, (cg, ng), (p64, p16, cnt), split_frame=split_frame)
         return p16, p64, cnt
 
     def bev_elev_partition(self, prm, elev_thresh, first_frame=0, last_frame=None, include_dyn=False, mark_dyn=False,
@@ -651,28 +665,17 @@ class DeviceStore:
         the only path that alters the store: the elevated points get dyn = 1 (owed re-transforms are flushed first).  The
         mark is made in THIS view's cells and persists: every later raster, of any view, treats these points as dynamic.
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
-        ctx, lib = self.ctx, self.ctx.lib
-        last_frame = self.n_frames if last_frame is None else last_frame
-        px = int(prm.px)
+        lib = self.ctx.lib
         if mark_dyn:
             self.flush_pending()                       # a call that must write: nothing stays owed
-        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
-        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
-        bound = self.max_window_points()
-        max_points = bound if max_points is None else max(int(max_points), 1)
-        ws = self._side_workspace('elev', lib.pca_bev_elev_workspace_bytes, max_points, px)
-        side = max(px, 1)
+        last_frame, max_points, call = self._window_pass(prm, first_frame, last_frame, max_points,
+                                                         side=('elev', lib.pca_bev_elev_workspace_bytes))
+        side = max(int(prm.px), 1)
         elev = torch.empty((side, side), dtype=torch.float64, device=self.device)
         obs = torch.empty((side, side), dtype=torch.uint8, device=self.device)
         flags = torch.empty(max_points, dtype=torch.uint8, device=self.device)
         counts = torch.empty(3, dtype=torch.int64, device=self.device)
-        st = self.c_store()
-        ctx.check(lib.pca_bev_elev_partition(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
-                                             self.head + last_frame, max_points, C.byref(prm), float(elev_thresh),
-                                             1 if include_dyn else 0, pend_T, pend_ends, n_pend, ws.data_ptr(),
-                                             ws.numel(), elev.data_ptr(), obs.data_ptr(), flags.data_ptr(),
-                                             counts.data_ptr(), ctx.stream()))
-        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        call(lib.pca_bev_elev_partition, (float(elev_thresh), 1 if include_dyn else 0), (elev, obs, flags, counts))
         lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
         lo, n = int(lo_hi[0]), min(int(lo_hi[1] - lo_hi[0]), max_points)
         flags = flags[:n]
@@ -691,28 +694,18 @@ class DeviceStore:
         int32 holding the u32 numbers of labelled points and of points of the winning label.
         The store is not written: owed re-transforms are applied to what the call reads and stay owed.
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
-        ctx, lib = self.ctx, self.ctx.lib
-        last_frame = self.n_frames if last_frame is None else last_frame
+        lib = self.ctx.lib
         px = int(prm.px)
         table = np.ascontiguousarray(label_of, dtype=np.uint8)
         if table.shape != (256, ):
             raise ValueError('label_of must hold 256 entries')
-        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
-        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
-        bound = self.max_window_points()
-        max_points = bound if max_points is None else max(int(max_points), 1)
-        ws = self._side_workspace('voxel', lib.pca_bev_voxel_workspace_bytes, max_points, px)
+        _, _, call = self._window_pass(prm, first_frame, last_frame, max_points, side=('voxel', lib.pca_bev_voxel_workspace_bytes))
         shape = (max(int(nz), 1), max(px, 1), max(px, 1))
         labels = torch.empty(shape, dtype=torch.uint8, device=self.device)
         counts = torch.empty(shape, dtype=torch.int32, device=self.device)
         top = torch.empty(shape, dtype=torch.int32, device=self.device)
-        st = self.c_store()
-        ctx.check(lib.pca_bev_voxel_labels(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
-                                           self.head + last_frame, max_points, C.byref(prm), float(z_lo), float(z_step),
-                                           int(nz), table.ctypes.data, int(n_labels), 1 if include_dyn else 0, pend_T,
-                                           pend_ends, n_pend, ws.data_ptr(), ws.numel(), labels.data_ptr(),
-                                           counts.data_ptr(), top.data_ptr(), ctx.stream()))
-        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        call(lib.pca_bev_voxel_labels, (float(z_lo), float(z_step), int(nz), table.ctypes.data, int(n_labels),
+                                        1 if include_dyn else 0), (labels, counts, top))
         return {'labels': labels, 'counts': counts, 'top': top}
 
     def bev_voxel_rays(self, prm, z_lo, z_step, nz, origins, first_frame=0, last_frame=None, include_dyn=False,
@@ -727,8 +720,7 @@ class DeviceStore:
         for a coordinate that is not finite (or beyond 2^30), rays dropped for more than 16 384 voxel steps.
         The store is not written: owed re-transforms are applied to what the call reads and stay owed.
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
-        ctx, lib = self.ctx, self.ctx.lib
-        last_frame = self.n_frames if last_frame is None else last_frame
+        last_frame, max_points, call = self._window_pass(prm, first_frame, last_frame, max_points)
         px = int(prm.px)
         if isinstance(origins, torch.Tensor):
             org = origins.to(device=self.device, dtype=torch.float64).contiguous()
@@ -736,21 +728,13 @@ class DeviceStore:
             org = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64)).to(self.device)
         if org.dim() != 2 or org.shape[1] != 3 or org.shape[0] != last_frame - first_frame:
             raise ValueError('origins must be [frames, 3], one row per frame of the range')
-        # the owed chain, read only (bev_pending flushes it when this window does not cover what is owed)
-        n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
-        bound = self.max_window_points()
-        max_points = bound if max_points is None else max(int(max_points), 1)
         shape = (max(int(nz), 1), max(px, 1), max(px, 1))
         seen = torch.empty(shape, dtype=torch.uint8, device=self.device)
         stats = torch.empty(4, dtype=torch.int64, device=self.device)
         if org.shape[0] == 0:
             org = torch.zeros((1, 3), dtype=torch.float64, device=self.device)     # (never read: a valid pointer)
-        st = self.c_store()
-        ctx.check(lib.pca_bev_voxel_rays(ctx.h, C.byref(st), self.frame_off.data_ptr(), self.head + first_frame,
-                                         self.head + last_frame, max_points, C.byref(prm), float(z_lo), float(z_step),
-                                         int(nz), 1 if include_dyn else 0, org.data_ptr(), pend_T, pend_ends, n_pend,
-                                         seen.data_ptr(), stats.data_ptr(), ctx.stream()))
-        self._k1_noted = None                      # (the call ran a noted K1 first: nothing is noted any more)
+        call(self.ctx.lib.pca_bev_voxel_rays, (float(z_lo), float(z_step), int(nz), 1 if include_dyn else 0, org.data_ptr()),
+             (seen, stats))
         return {'seen': seen, 'stats': stats}
 
     def bev_many(self, jobs, out16):

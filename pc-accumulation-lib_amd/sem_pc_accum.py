@@ -324,6 +324,16 @@ class SemanticPointCloudAccumulator:
         """(pcs, trajs) of one sample as generate_bev builds them (overridden where other agents' trajectories exist)."""
         return self._window_inputs(present_idx, gen_future)
 
+    def _unaugmented_part(self, present_idx, part):
+        """(pc, rot_mat, view) of `part` ('present' | 'future' | 'full') of the sample generate_bev(present_idx, 1, True) would
+        make, un-augmented: heading from the last two present poses, no shift, zoom 1."""
+        if part not in ('present', 'future', 'full'):
+            raise ValueError("part must be 'present', 'future' or 'full'")
+        self.store.poll_status()
+        pcs, trajs = self._window_inputs_for(present_idx, True)
+        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
+        return pcs['pc_' + part], rot_mat, 1. * self.sem_bev_generator.view_size
+
     def partition_by_elev(self, present_idx, elev_thresh, part='full', mark_dyn=False):
         """Extension (the reference's static_obj_partitioning_by_elev, sem_bev.py:556-591, on the device window): the points
         of `part` ('present' | 'future' | 'full') of the sample generate_bev(present_idx, 1, True) would make, partitioned by
@@ -332,14 +342,9 @@ class SemanticPointCloudAccumulator:
         cuda tensors; 'elev' of part='present' is the f64 elevation plane of that sample.  What KITTI needs, where no
         instance labels exist and dyn is 0 everywhere: mark_dyn=True sets dyn = 1 for the elevated points, in the store,
         for good -- they then stay out of the medians, the elevation and the intensity planes of every later sample."""
-        if part not in ('present', 'future', 'full'):
-            raise ValueError("part must be 'present', 'future' or 'full'")
-        gen = self.sem_bev_generator
-        self.store.poll_status()
-        pcs, trajs = self._window_inputs_for(present_idx, True)
-        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
-        return gen.elev_partition_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, elev_thresh,
-                                         include_dyn=False, mark_dyn=mark_dyn)
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        return self.sem_bev_generator.elev_partition_device(pc, rot_mat, 0., 0., view, elev_thresh, include_dyn=False,
+                                                            mark_dyn=mark_dyn)
 
     def voxel_labels(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False):
         """Extension (no reference counterpart): semantic occupancy labels of `part` ('present' | 'future' | 'full') of the
@@ -349,14 +354,9 @@ class SemanticPointCloudAccumulator:
         class for the classes 0 .. 31.  Returns DeviceStore.bev_voxel_labels' dict of cuda tensors 'labels', 'counts',
         'top', each [nz, px, px]; labels 255 = no point in the voxel (free or unseen is not decided here: voxel_occupancy).
         Nothing is written: the store, the owed re-transforms and every later sample stay as they are."""
-        if part not in ('present', 'future', 'full'):
-            raise ValueError("part must be 'present', 'future' or 'full'")
-        gen = self.sem_bev_generator
-        self.store.poll_status()
-        pcs, trajs = self._window_inputs_for(present_idx, True)
-        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
-        return gen.voxel_labels_device(pcs['pc_' + part], rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, classes=classes,
-                                       include_dyn=include_dyn)
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        return self.sem_bev_generator.voxel_labels_device(pc, rot_mat, 0., 0., view, z_range, nz, classes=classes,
+                                                          include_dyn=include_dyn)
 
     def voxel_occupancy(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False,
                         origins=None):
@@ -370,22 +370,13 @@ class SemanticPointCloudAccumulator:
         int64 [4]; 'state' uint8 [nz, px, px]: 2 = occupied (counts > 0), else 1 = free (a ray passed through), else
         0 = unseen (what semantic-scene-completion training has to ignore).  Nothing is written to the store."""
         import torch
-        if part not in ('present', 'future', 'full'):
-            raise ValueError("part must be 'present', 'future' or 'full'")
         gen = self.sem_bev_generator
-        self.store.poll_status()
-        pcs, trajs = self._window_inputs_for(present_idx, True)
-        rot_mat = hl.rotation_matrix_3d(hl.heading_rot_ang(trajs['ego_traj_present']))
-        pc = pcs['pc_' + part]
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
         if origins is None:
-            w = pc.window
-            f0, f1 = {'present': (w.first, w.split), 'future': (w.split, w.last), 'full': (w.first, w.last)}[part]
-            if w.future_is_present:
-                f0, f1 = w.first, w.last
-            origins = self._track.as_array()[f0:f1]
-        out = gen.voxel_labels_device(pc, rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, classes=classes,
-                                      include_dyn=include_dyn)
-        out.update(gen.voxel_rays_device(pc, origins, rot_mat, 0., 0., 1. * gen.view_size, z_range, nz, include_dyn=include_dyn))
+            lo, hi = pc.frames()
+            origins = self._track.as_array()[lo:hi]
+        out = gen.voxel_labels_device(pc, rot_mat, 0., 0., view, z_range, nz, classes=classes, include_dyn=include_dyn)
+        out.update(gen.voxel_rays_device(pc, origins, rot_mat, 0., 0., view, z_range, nz, include_dyn=include_dyn))
         out['state'] = torch.where(out['counts'] != 0, 2, out['seen'].to(torch.int32)).to(torch.uint8)
         return out
 

@@ -9,19 +9,12 @@ import numpy as np
 import pytest
 
 import elev_partition_common as ec
-from test_gpu_kernels import DYNOBJ, KITTI_FILTERS, SEM_IDXS, T, dev_store  # noqa: F401  (T: fixture)
+from test_gpu_kernels import SEM_IDXS, T, dev_store  # noqa: F401  (T: fixture)
+from window_pass_common import BEV_KITTI, INTS, kitti_accumulator, params
 
 pytestmark = pytest.mark.gpu
 
-INTS = (20., 20., 0.5)
-BEV_KITTI = dict(type='sem', view_size=30, pixel_size=32, max_trans_radius=0., zoom_thresh=0., do_warp=False,
-                 int_scaler=20., int_sep_scaler=20., int_mid_threshold=0.5, height_filter=None)
 CASE_NAMES = [c[0] for c in ec.CASES]
-
-
-def params(origin, R, dx, dy, view, px, hf):
-    from pca_amd.device_store import make_bev_params
-    return make_bev_params(origin, R, dx, dy, view, px, hf, *INTS, 0, DYNOBJ, False)
 
 
 def host(out):
@@ -128,29 +121,6 @@ def test_owed_chain_is_applied_to_what_is_read_and_stays_owed(T, k):
 
 
 # ---------------------------------------------------------------------------------------------- 4 and 7: the KITTI drop-in
-def kitti_accumulator(tmp_path, bev_params, n_frames):
-    import os
-
-    from fake_kitti import SEQ, write_tree
-
-    from datasets.kitti360_utils import get_camera_intrinsics, get_transf_matrices
-    from kitti360_sem_pc_accum import Kitti360SemanticPointCloudAccumulator
-    from obs_dataloaders.kitti360_obs_dataloader import Kitti360Dataloader
-    root = str(tmp_path / 'KITTI-360')
-    if not os.path.isdir(root):
-        write_tree(root, first_idx=0, n_frames=n_frames)
-    _, h_velo_cam = get_transf_matrices(root)
-    p_cam = get_camera_intrinsics(root)
-    calib = {'h_velo_cam': h_velo_cam, 'p_cam_frame': p_cam, 'p_velo_frame': np.matmul(p_cam, h_velo_cam)}
-    Ts = np.load(os.path.join(root, 'T_new_prev.npy'))
-    acc = Kitti360SemanticPointCloudAccumulator(50., calib, 1e3, 'none', KITTI_FILTERS, SEM_IDXS, True, bev_params)
-    it = iter(Ts)
-    acc.pose_provider = lambda pc: next(it)
-    for observations in Kitti360Dataloader(root, 1, [SEQ], [0], [n_frames]):
-        acc.integrate(observations)
-    return acc
-
-
 def test_noted_k1_runs_before_the_partition(T, tmp_path, monkeypatch):
     prm = params((0., 0., 0.), ec.rotation(0.3), 0., 0., 50., 32, None)
     out = []

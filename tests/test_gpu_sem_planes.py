@@ -1,28 +1,19 @@
 """GPU: BEV planes of any semantic class group (pca_bev_class_planes, DeviceStore.bev_class_planes, SemBEVGenerator
 sem_planes / gen_sem_probmap / gen_gridmap_count_map) against the reference's fixture, the main raster, the C oracle
 (pinned per group by tests/test_sem_planes_golden.py) and plain numpy."""
-import os
 import pickle
 import random
 
 import numpy as np
 import pytest
 
-from test_gpu_kernels import DYNOBJ, KITTI_FILTERS, SEM_IDXS, T, dev_store, orc  # noqa: F401  (T, orc: fixtures)
+from test_gpu_kernels import DYNOBJ, SEM_IDXS, T, dev_store, orc  # noqa: F401  (T, orc: fixtures)
+from window_pass_common import BEV_KITTI, INTS, kitti_accumulator, params
 
 pytestmark = pytest.mark.gpu
 
 SETS = ('present', 'future', 'full')
-INTS = (20., 20., 0.5)
-BEV_KITTI = dict(type='sem', view_size=30, pixel_size=32, max_trans_radius=0., zoom_thresh=0., do_warp=False,
-                 int_scaler=20., int_sep_scaler=20., int_mid_threshold=0.5, height_filter=None)
 SEM_PLANES = {'sidewalk': [1], 'vehicle': ['car', 'truck', 'bus', 'motorcycle'], 'roadway': ['road']}
-
-
-def params(origin, rot, dx, dy, view, px, hf, dyn=DYNOBJ):
-    from pca_amd import host_logic as hl
-    from pca_amd.device_store import make_bev_params
-    return make_bev_params(origin, hl.rotation_matrix_3d(rot), dx, dy, view, px, hf, *INTS, 0, dyn, False)
 
 
 def closed_form(n, n_g):
@@ -204,31 +195,6 @@ def test_owed_chain_is_applied_to_what_is_read_and_stays_owed(T, orc, k):
 
 
 # ---------------------------------------------------------------------------------------------- 5 and 7: the KITTI drop-in
-def kitti_tree(tmp_path, n_frames=10):
-    from fake_kitti import SEQ, write_tree
-
-    from datasets.kitti360_utils import get_camera_intrinsics, get_transf_matrices
-    root = str(tmp_path / 'KITTI-360')
-    if not os.path.isdir(root):
-        write_tree(root, first_idx=0, n_frames=n_frames)
-    _, h_velo_cam = get_transf_matrices(root)
-    p_cam = get_camera_intrinsics(root)
-    calib = {'h_velo_cam': h_velo_cam, 'p_cam_frame': p_cam, 'p_velo_frame': np.matmul(p_cam, h_velo_cam)}
-    return root, SEQ, calib, np.load(os.path.join(root, 'T_new_prev.npy'))
-
-
-def kitti_accumulator(tmp_path, bev_params, n_frames=10):
-    from kitti360_sem_pc_accum import Kitti360SemanticPointCloudAccumulator
-    from obs_dataloaders.kitti360_obs_dataloader import Kitti360Dataloader
-    root, seq, calib, Ts = kitti_tree(tmp_path, n_frames)
-    acc = Kitti360SemanticPointCloudAccumulator(50., calib, 1e3, 'none', KITTI_FILTERS, SEM_IDXS, True, bev_params)
-    it = iter(Ts)
-    acc.pose_provider = lambda pc: next(it)
-    for observations in Kitti360Dataloader(root, 1, [seq], [0], [n_frames]):
-        acc.integrate(observations)
-    return acc
-
-
 def test_noted_k1_runs_before_the_class_planes(T, tmp_path, monkeypatch):
     groups = [[0], DYNOBJ, [1]]
     prm = params((0., 0., 0.), 0.3, 0., 0., 50., 32, None)

@@ -9,18 +9,13 @@ import pytest
 
 import test_voxel_labels_model as hand
 import voxel_labels_common as vc
-from test_gpu_kernels import DYNOBJ, SEM_IDXS, T, dev_store  # noqa: F401  (T: fixture)
+from test_gpu_kernels import SEM_IDXS, T, dev_store  # noqa: F401  (T: fixture)
+from window_pass_common import BEV_KITTI, frames_of, kitti_accumulator, loaded, params
 
 pytestmark = pytest.mark.gpu
 
-INTS = (20., 20., 0.5)
 SHAPES = [(5, 1, 1), (8, 5, 19), (20, 5, 19), (20, 32, 32), (64, 32, 32), (64, 7, 20)]
 ORIGIN, VIEW = (0.3, -0.2, 0.125), 40.
-
-
-def params(origin, R, dx, dy, view, px, hf):
-    from pca_amd.device_store import make_bev_params
-    return make_bev_params(origin, R, dx, dy, view, px, hf, *INTS, 0, DYNOBJ, False)
 
 
 def table_for(n_labels):
@@ -33,25 +28,6 @@ def table_for(n_labels):
     else:
         t[:19] = n_labels - 1 - np.arange(19)
     return t
-
-
-_frames = {}
-
-
-def frames_of(seed):
-    """Three frames of 4 000 random rows (z on a 1/1024 lattice), made once per seed and never changed."""
-    if seed not in _frames:
-        rng = np.random.default_rng(seed)
-        _frames[seed] = [vc.random_rows(rng, 4000, 25.) for _ in range(3)]
-        for f in _frames[seed]:
-            f.setflags(write=False)
-    return _frames[seed]
-
-
-def loaded(frames, capacity=1 << 15, max_frames=8):
-    st = dev_store(capacity=capacity, max_frames=max_frames)
-    assert st.load_rows(frames) is None
-    return st
 
 
 # ---------------------------------------------------------------------------------------------- 1: the model, small shapes
@@ -396,7 +372,6 @@ def check_dropin(T, acc, idx):
 
 
 def test_kitti_dropin(T, tmp_path):
-    from test_gpu_elev_partition import BEV_KITTI, kitti_accumulator
     check_dropin(T, kitti_accumulator(tmp_path, dict(BEV_KITTI), n_frames=14), 9)
 
 

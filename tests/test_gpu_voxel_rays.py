@@ -10,32 +10,14 @@ import pytest
 
 import voxel_labels_common as vc
 import voxel_rays_common as rc
-from test_gpu_kernels import DYNOBJ, SEM_IDXS, T, dev_store  # noqa: F401  (T: fixture)
+from test_gpu_kernels import T  # noqa: F401  (T: fixture)
+from window_pass_common import BEV_KITTI, frames_of, kitti_accumulator, loaded, owe, params
 
 pytestmark = pytest.mark.gpu
 
-INTS = (20., 20., 0.5)
 SHAPES = [(5, 1), (8, 5), (20, 32), (64, 32), (64, 7)]
 ORIGIN, VIEW = (0.3, -0.2, 0.125), 40.
 SENSORS = np.array([[1.0, 2.0, 0.5], [-8.0, 5.0, 1.0], [30.0, -3.0, 0.75]])      # the third one lies outside the view
-
-
-def params(origin, R, dx, dy, view, px, hf=None):
-    from pca_amd.device_store import make_bev_params
-    return make_bev_params(origin, R, dx, dy, view, px, hf, *INTS, 0, DYNOBJ, False)
-
-
-_frames = {}
-
-
-def frames_of(seed):
-    """Three frames of 4 000 random rows within +-25 m (z on a 1/1024 lattice), made once per seed and never changed."""
-    if seed not in _frames:
-        rng = np.random.default_rng(seed)
-        _frames[seed] = [rc.random_rows(rng, 4000, 25.) for _ in range(3)]
-        for f in _frames[seed]:
-            f.setflags(write=False)
-    return _frames[seed]
 
 
 _wants = {}
@@ -46,12 +28,6 @@ def want_of(key, *args):
     if key not in _wants:
         _wants[key] = rc.model(*args)
     return _wants[key]
-
-
-def loaded(frames, capacity=1 << 15, max_frames=8):
-    st = dev_store(capacity=capacity, max_frames=max_frames)
-    assert st.load_rows(frames) is None
-    return st
 
 
 # ---------------------------------------------------------------------------------------------- 1: the model, small shapes
@@ -109,12 +85,6 @@ def test_exact_ties_on_a_lattice(T, turn):
 
 
 # ---------------------------------------------------------------------------------------------- 2: owed transforms
-def owe(st, Tm, n_frames):
-    """Notes transform Tm as owed by the first n_frames frames of the store (what retransform(defer=True) notes when the
-    store holds that many frames)."""
-    st._pending.append((np.ascontiguousarray(Tm, dtype=np.float64).reshape(16).copy(), st.head + n_frames))
-
-
 @pytest.mark.parametrize('ends', [(2, ), (1, 2, 2, 3)])
 def test_owed_chain_over_part_of_the_window(T, ends):
     from test_gpu_kernels import _tilting_transform
@@ -285,7 +255,6 @@ def test_refusals_launch_nothing_and_leave_the_outputs_alone(T):
 # ---------------------------------------------------------------------------------------------- 5: the top level
 def test_generator_forms_and_voxel_occupancy_on_a_kitti_sequence(T, tmp_path):
     from pca_amd import host_logic as hl
-    from test_gpu_elev_partition import BEV_KITTI, kitti_accumulator
     acc, idx = kitti_accumulator(tmp_path, dict(BEV_KITTI), n_frames=14), 9
     gen = acc.sem_bev_generator
     z_range, nz, classes = (-2.0, 4.4), 32, [[0, 1, 2], [13, 14, 15, 17], [5], [8, 9]]
