@@ -520,6 +520,45 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The window of the store rendered into a pinhole camera with a z-buffer: dense depth, colour and class targets for an
+ *       image (what KITTI depth completion calls accumulated lidar ground truth).  The projection and its mask are the
+ *       reference's velo2frame + velo2img, sem_pc_accum.py:347-402, on the stored f64 coordinates (owed re-transforms
+ *       applied, oldest first) -- the expressions K1 evaluates; the z-buffer itself has no reference counterpart.
+ *     cam->P: row-major 3x4, store coordinates -> image, as p_velo_frame.  fx, fy, d = the rows of P as f64 fma chains in
+ *       k order; d == 0 -> -1e-6; u = rint(fx / |d|), v = rint(fy / |d|) (IEEE divide).  A point is KEPT iff 0 <= u < width,
+ *       0 <= v < height, d > min_depth and d < max_depth (0 and +inf: the reference's mask); a NaN anywhere drops it.
+ *     include_dyn == 0: points with dyn == 1 take no part.  only != NULL: neither do points whose class is not in the set.
+ *     A kept point competes for every pixel (u + du, v + dv), |du|, |dv| <= radius, that lies inside the image (a square
+ *       footprint, clipped, not wrapped; the centre decides whether the point takes part).  A pixel goes to the point with
+ *       the smallest (float)d and, among equal ones, the smallest index in the window: the result does not depend on the
+ *       order in which points arrive.
+ *     Output (dev, all needed; keys is scratch): depth f32 [H][W] ((float)d of the winner, 0 where no point), index i64 [H][W]
+ *       (the winner's index relative to the window's first point, -1 where none), rgb u8 [H][W][3] and sem u8 [H][W] (the
+ *       winner's colour and class; 0, 0, 0 and 255 where none), stats i64 [3]: points considered (past the dyn and class
+ *       filters), points kept by the mask, pixels covered.
+ *     Scope: no lens distortion; ONE P per call (no per-frame camera poses); no hidden-point removal beyond the footprint.
+ *     Limits: 1 <= width, height, width * height <= 2^24; 0 <= radius <= 3; 0 <= min_depth < max_depth; every entry of P
+ *       finite; max_points < 2^32; slot_begin <= slot_end.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to the points that are read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a
+ *     bin range armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared.  A window above max_points is
+ *     cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives the empty image.  Every argument is
+ *     checked before anything is launched; -1 with pca_last_error set ("render camera: ...").
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    double P[12];              /* row-major 3x4: store coordinates -> image, as p_velo_frame */
+    int32_t width, height, radius, include_dyn;
+    double min_depth, max_depth;
+} pca_camera;
+int pca_render_camera(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                      int slot_begin, int slot_end, int64_t max_points, const pca_camera *cam,
+                      const pca_class_group *only /* NULL: every class */,
+                      const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                      uint64_t *keys /* dev [H][W], scratch */, float *depth /*dev [H][W]*/, int64_t *index /*dev [H][W]*/,
+                      uint8_t *rgb /* dev [H][W][3] */, uint8_t *sem /*dev [H][W]*/, int64_t *stats /* dev [3] */,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -858,7 +897,7 @@ enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
     PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
     PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS,
-    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_COUNT
+    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_RENDER_ZBUFFER, PCA_K_RENDER_RESOLVE, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

@@ -147,20 +147,23 @@ static inline int bev_fill_owed(pca_ctx *ctx, const char *what, const double *pe
 }
 
 // ---- host side: a read-only pass over a window of the store (the class planes, the elevation partition, the occupancy labels,
-// the rays through the voxel grid; the next pass of the family starts here).  The main raster has its own checks. ----
+// the rays through the voxel grid, the camera render of pca_render.hip; the next pass of the family starts here).  The main
+// raster has its own checks. ----
 #define SIDE_PX_MAX 1024          // the largest grid of these passes (no banding)
 // what: the message prefix; rgbs: the pass reads the class byte; split: its window has a slot_split
 struct WindowPass { const char *what; bool rgbs, split; };
-// The checks every entry point shares, before anything is launched: the pointers (own_ok: those of the pass's own arguments),
-// the store's arrays, the slot order, px, the rotation, the owed chain -- and the fields every argument block has (Args:
-// SideArgs or RayArgs; a pass without a split hands slot_begin in its place).
-template <typename Args>
-static inline int window_check(pca_ctx *ctx, const WindowPass &pass, bool own_ok, const pca_store *store, const int64_t *frame_off,
-                               int slot_begin, int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm,
-                               const double *pending_Ts, const int *pending_slot_ends, int n_pending, Args &A)
+// The checks every entry point shares, before anything is launched, whatever the pass renders into (a BEV grid or a camera
+// image): the pointers (own_ok: those of the pass's own arguments, its parameter block included), the store's arrays, the slot
+// order, then the pass's own `target` check (a callable returning 0 or -1 with ctx->err set: the grid of the BEV passes),
+// the owed chain -- and the fields every argument block has (Args: SideArgs, RayArgs or RenderArgs; a pass without a split
+// hands slot_begin in its place).
+template <typename Args, typename Target>
+static inline int window_check_any(pca_ctx *ctx, const WindowPass &pass, bool own_ok, const pca_store *store, const int64_t *frame_off,
+                                   int slot_begin, int slot_split, int slot_end, int64_t max_points, Target target,
+                                   const double *pending_Ts, const int *pending_slot_ends, int n_pending, Args &A)
 {
     const std::string w(pass.what);
-    if (!store || !frame_off || !prm || !own_ok) { ctx->err = w + ": bad arguments"; return -1; }
+    if (!store || !frame_off || !own_ok) { ctx->err = w + ": bad arguments"; return -1; }
     if (!store->x || !store->y || !store->z || (pass.rgbs && !store->rgbs) || !store->dyn) {
         ctx->err = w + ": the store's x, y, z" + (pass.rgbs ? ", rgbs" : "") + " and dyn arrays are needed";
         return -1;
@@ -169,15 +172,29 @@ static inline int window_check(pca_ctx *ctx, const WindowPass &pass, bool own_ok
         ctx->err = w + (pass.split ? ": need slot_begin <= slot_split <= slot_end" : ": need slot_begin <= slot_end");
         return -1;
     }
-    if (prm->px < 1 || prm->px > SIDE_PX_MAX) { ctx->err = w + ": px must be in 1..1024"; return -1; }
-    if (bev_check_rotation(ctx, pass.what, prm)) return -1;
+    if (target()) return -1;
     if (bev_fill_owed(ctx, pass.what, pending_Ts, pending_slot_ends, n_pending, slot_begin, slot_end, A.owed)) return -1;
     A.st = *store;
     A.frame_off = frame_off;
     A.slot_begin = slot_begin; A.slot_end = slot_end;
     A.max_points = max_points;
-    A.prm = *prm;
     A.status = ctx->ticket + 1;
+    return 0;
+}
+// ... of a pass over a BEV grid: px and the rotation between the slot order and the owed chain, prm into the block.
+template <typename Args>
+static inline int window_check(pca_ctx *ctx, const WindowPass &pass, bool own_ok, const pca_store *store, const int64_t *frame_off,
+                               int slot_begin, int slot_split, int slot_end, int64_t max_points, const pca_bev_params *prm,
+                               const double *pending_Ts, const int *pending_slot_ends, int n_pending, Args &A)
+{
+    auto grid = [&]() -> int {
+        if (prm->px < 1 || prm->px > SIDE_PX_MAX) { ctx->err = std::string(pass.what) + ": px must be in 1..1024"; return -1; }
+        return bev_check_rotation(ctx, pass.what, prm);
+    };
+    if (window_check_any(ctx, pass, prm && own_ok, store, frame_off, slot_begin, slot_split, slot_end, max_points, grid,
+                         pending_Ts, pending_slot_ends, n_pending, A))
+        return -1;
+    A.prm = *prm;
     return 0;
 }
 // the voxel grid of the occupancy labels and of the rays: nz height bins of z_step from z_lo

@@ -344,6 +344,16 @@ class Kitti360SemanticPointCloudAccumulator(SemanticPointCloudAccumulator):
             self._store = main
         return rows, [0., 0., 0.], semseg, T_new_prev
 
+    def _render_defaults(self):
+        """render_camera's defaults: calib_params['p_velo_frame'] and the size of the last integrated image.  The stored cloud
+        is kept in the newest frame's lidar coordinates, so this is the accumulated cloud as the newest camera sees it."""
+        rgb = self.rgbs[-1] if self.rgbs else None
+        if rgb is None:
+            return self.P_velo_frame, None
+        if hasattr(rgb, 'shape'):                       # an array, a tensor or a pca_amd.ingest.DeviceImage: [H, W, 3]
+            return self.P_velo_frame, (int(rgb.shape[1]), int(rgb.shape[0]))
+        return self.P_velo_frame, tuple(int(v) for v in rgb.size)       # a PIL image: (W, H)
+
     # ---- BEV -----------------------------------------------------------------------------------
     def generate_bev(self, present_idx: int = None, bev_num: int = 1, gen_future: bool = False):
         if bev_num == 1 and gen_future and self._fast_bev_ok(present_idx):

@@ -56,6 +56,7 @@ class DeviceStore:
         # scratch of bev_class_planes, of bev_elev_partition and of bev_voxel_labels, each its own (a main raster may have sized
         # _ws differently): name -> [buffer, the points it is sized for, px], see _side_workspace
         self._ws_side = {}
+        self._render_keys = {}           # (H, W) -> the z-buffer's keys (render_camera)
         self._dedup_ws = None
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
@@ -609,7 +610,8 @@ class DeviceStore:
 
     def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None):
         """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
-        bev_elev_partition, bev_voxel_labels, bev_voxel_rays; the next pass of the family starts here): last_frame's default,
+        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, render_camera -- whose `prm` is its camera block; the next pass
+        of the family starts here): last_frame's default,
         the bound at which the window is cut (max_points; default: the live window's own) and -- side = (name,
         pca_*_workspace_bytes) -- the pass's scratch.  Returns (last_frame, max_points, call).
         call(fn, own, outs, split_frame=None) is the one C call
@@ -736,6 +738,38 @@ class DeviceStore:
         call(self.ctx.lib.pca_bev_voxel_rays, (float(z_lo), float(z_step), int(nz), 1 if include_dyn else 0, org.data_ptr()),
              (seen, stats))
         return {'seen': seen, 'stats': stats}
+
+    def render_camera(self, cam, first_frame=0, last_frame=None, classes=None, max_points=None):
+        """The stored points of the live frames [first_frame, last_frame) rendered into a pinhole camera with a z-buffer
+        (pca_render_camera).  cam: _lib.make_camera(P, width, height, radius, include_dyn, depth_range), P 3x4 from the
+        store's current coordinates to the image, as p_velo_frame.  A point is projected as K1 projects (the reference's
+        velo2frame + velo2img on the stored f64 coordinates) and dropped if it falls outside the image or the open depth
+        range, if include_dyn is off and dyn == 1, or if `classes` (a list of class indices; None: every class) does not
+        hold its class.  A kept point competes for the pixels of its square footprint of half side cam.radius, clipped to
+        the image; a pixel goes to the smallest depth rounded to float32 and, of equal depths, to the smallest index in
+        the window, so the result does not depend on the order in which points arrive.
+        Returns a dict of cuda tensors: 'depth' float32 [H, W] (0 where no point); 'index' int64 [H, W], the winner's index
+        relative to the window's first point (-1 where none); 'rgb' uint8 [H, W, 3] and 'sem' uint8 [H, W], the winner's
+        colour and class (0 and 255 where none); 'stats' int64 [3]: points considered, points kept, pixels covered.
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        _, _, call = self._window_pass(cam, first_frame, last_frame, max_points)
+        H, W = max(int(cam.height), 1), max(int(cam.width), 1)
+        only = None
+        if classes is not None:
+            only = _lib.PcaClassGroup()
+            only.mask[:] = list(_lib.class_mask(classes))
+        shape = (H, W) if H * W <= 1 << 24 else (1, 1)      # (a larger image is refused by the call: nothing to allocate for it)
+        keys = self._render_keys.get(shape)
+        if keys is None:
+            keys = self._render_keys[shape] = torch.empty(shape, dtype=torch.int64, device=self.device)
+        depth = torch.empty(shape, dtype=torch.float32, device=self.device)
+        index = torch.empty(shape, dtype=torch.int64, device=self.device)
+        rgb = torch.empty(shape + (3, ), dtype=torch.uint8, device=self.device)
+        sem = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(3, dtype=torch.int64, device=self.device)
+        call(self.ctx.lib.pca_render_camera, (only, ), (keys, depth, index, rgb, sem, stats))
+        return {'depth': depth, 'index': index, 'rgb': rgb, 'sem': sem, 'stats': stats}
 
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters

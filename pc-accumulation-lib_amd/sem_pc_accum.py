@@ -380,6 +380,39 @@ class SemanticPointCloudAccumulator:
         out['state'] = torch.where(out['counts'] != 0, 2, out['seen'].to(torch.int32)).to(torch.uint8)
         return out
 
+    def _render_defaults(self):
+        """(P, (W, H)) of render_camera where the dataset has one camera the stored coordinates belong to; (None, None) here."""
+        return None, None
+
+    def render_camera(self, P=None, size=None, frames=None, radius=0, depth_range=(0., np.inf), classes=None,
+                      include_dyn=True):
+        """Extension (the reference's velo2frame + velo2img, sem_pc_accum.py:347-402, over the whole accumulated cloud, with a
+        z-buffer): the stored points of the live frames `frames` = (lo, hi) (default: all of them) rendered into a pinhole
+        camera -- dense depth, colour and class targets for an image.  P: 3x4, from the STORE's coordinates to the image,
+        as p_velo_frame; size = (W, H).  Both are required here: NuScenes stores world coordinates, so a camera with
+        intrinsics K and pose T_world_from_cam has P = K [I|0] inv(T_world_from_cam); the KITTI class has defaults.
+        A point outside the image or the open interval depth_range is dropped, so is one of a class outside `classes` (a list
+        of class indices; None: every class) and, with include_dyn=False, one with dyn == 1.  A kept point competes for the
+        pixels within `radius` (0..3) of its own, a square footprint clipped to the image: the splat keeps the background
+        from showing through the gaps of a sparse foreground.  A pixel goes to the smallest depth rounded to float32, of
+        equal depths to the point stored first.  One P per call and no lens distortion.
+        Returns DeviceStore.render_camera's dict of cuda tensors: 'depth' float32 [H, W] (0: no point), 'index' int64 [H, W]
+        (the winner's index among the points of `frames`, -1: none), 'rgb' uint8 [H, W, 3], 'sem' uint8 [H, W] (255: none),
+        'stats' int64 [3] = points considered, kept, pixels covered.
+        Nothing is written: the store, the owed re-transforms and every later sample stay as they are."""
+        from pca_amd._lib import make_camera
+        self.store.poll_status()
+        dflt_P, dflt_size = self._render_defaults() if P is None or size is None else (None, None)
+        P = dflt_P if P is None else P
+        size = dflt_size if size is None else size
+        if P is None or size is None:
+            raise ValueError('render_camera needs P (3x4, store coordinates -> image) and size = (W, H)')
+        lo, hi = (0, self.store.n_frames) if frames is None else frames
+        if not 0 <= lo <= hi <= self.store.n_frames:
+            raise ValueError('frames must be a range (lo, hi) of live frames')
+        cam = make_camera(np.asarray(P, dtype=np.float64)[:3], size[0], size[1], radius, include_dyn, depth_range)
+        return self.store.render_camera(cam, lo, hi, classes=classes)
+
     def generate_bev_many(self, present_idxs, gen_future: bool = True):
         """Extension (no reference counterpart): the samples generate_bev(idx, 1, gen_future)[0] would return for every idx of
         `present_idxs`, rasterised in ONE launch of each kernel (the store does not change between them: the driver's sweep
