@@ -520,6 +520,59 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Free-space carving by ray hit / miss: the counting form of pca_bev_voxel_rays.  A voxel that held points of a movable
+ *       class at one moment, and that the beams of other frames later passed straight through, held a moving object; its
+ *       points are flagged.  No reference counterpart.  What KITTI needs, where no instance labels exist and dyn is 0 for
+ *       every point, and a second opinion for the classes the NuScenes tracker does not follow.
+ *     Geometry, ray set-up, drop rules, traversal order and tie order are word for word those of pca_bev_voxel_rays (f64,
+ *       nothing fused, the unfused product sum, IEEE divisions; a ray with a coordinate that is not finite or >= 2^30 in
+ *       magnitude is dropped, so is one over PCA_BEV_RAYS_MAX_STEPS; Amanatides-Woo driven by the integer step counts, axes
+ *       in the order (u, v, w); the place of voxel (i, j, k) in the output is [k][px - 1 - j][i]).
+ *     A point TAKES PART iff it lies inside the window cut at max_points and (include_dyn != 0 or dyn != 1).  Every point that
+ *       takes part has a ray from its slot's origin to itself; if that ray is not dropped it is CAST.
+ *     hits[v]: the number of cast rays whose end voxel is v and lies inside the grid.  The class, the crop and height_filter
+ *       play no part, as in the rays pass.
+ *     A CANDIDATE POINT is a point with a cast ray, an end voxel inside the grid and a class in `only`; a CANDIDATE VOXEL holds
+ *       at least one candidate point.
+ *     cross[v], for a candidate voxel: the number of cast rays that have a traversal step `it` (0-based, of N) with
+ *       it < N - end_margin at voxel v.  A ray visits a voxel at most once, and its end voxel is never counted by itself.
+ *       cross[v] is 0 for every voxel that is NOT a candidate voxel (the kernel counts only where it has to).
+ *     A candidate point in voxel v is FLAGGED iff cross[v] >= min_cross and (double)cross[v] >= ratio * (double)hits[v]: one
+ *       f64 multiply and one compare.
+ *     Output (dev, any of them may be NULL, not all; hits, cross and stats are cleared by the call itself, on the stream):
+ *       hits, cross u32 [nz][px][px]; flags u8 [window points] in window order: 1 flagged, 0 candidate kept, 255 everything
+ *       else (every byte of the cut window is written exactly once, bytes beyond the cut are not written);
+ *       stats i64 [6]: points that take part, rays cast, dropped not finite, dropped too long, candidate points, flagged
+ *       points.  All sums are integer sums: the result does not depend on the order of the points.
+ *     Scope: ONE origin per stored frame; the rays of a point's own frame count like any other -- end_margin is what keeps a
+ *       surface from carving itself (neighbouring beams of one surface cross its voxels just before they end), and ratio is
+ *       what keeps a surface that is hit as often as it is crossed; no automatic call from integrate().
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view and px are read.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32; z_lo finite; z_step finite and > 0; 0 <= end_margin <= PCA_BEV_RAYS_MAX_STEPS;
+ *       min_cross >= 1; ratio finite and >= 0; origins and only not NULL; workspace of pca_bev_carve_workspace_bytes(max_points,
+ *       px, nz) bytes; max_points < 2^32; slot_begin <= slot_end.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to the points that are read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a
+ *     bin range armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared.  A window above max_points is
+ *     cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives all zeros and writes no flags.  Every
+ *     argument is checked before anything is launched; -1 with pca_last_error set ("bev voxel carve: ..."), nothing written.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t pca_bev_carve_workspace_bytes(int64_t max_points, int px, int nz);
+int pca_bev_voxel_carve(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                        int slot_begin, int slot_end, int64_t max_points,
+                        const pca_bev_params *prm, double z_lo, double z_step, int nz, int include_dyn,
+                        const double *origins /*dev [slot_end - slot_begin][3]: sensor position of each slot, as pca_bev_voxel_rays takes them*/,
+                        const pca_class_group *only /*the classes that may be flagged; not NULL*/,
+                        int end_margin, uint32_t min_cross, double ratio,
+                        const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                        void *workspace /*dev*/, int64_t workspace_bytes,
+                        uint32_t *hits  /*dev [nz][px][px] or NULL*/,
+                        uint32_t *cross /*dev [nz][px][px] or NULL*/,
+                        uint8_t  *flags /*dev [window points] or NULL: 1 flagged, 0 candidate kept, 255 everything else*/,
+                        int64_t  *stats /*dev [6] or NULL*/,
+                        void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The window of the store rendered into a pinhole camera with a z-buffer: dense depth, colour and class targets for an
  *       image (what KITTI depth completion calls accumulated lidar ground truth).  The projection and its mask are the
  *       reference's velo2frame + velo2img, sem_pc_accum.py:347-402, on the stored f64 coordinates (owed re-transforms
@@ -897,7 +950,8 @@ enum {
     PCA_K_KITTI = 0, PCA_K_NUSC, PCA_K_PROJECT_CAMS, PCA_K_RETRANSFORM, PCA_K_MARK_DYNAMIC,
     PCA_K_BEV_BIN, PCA_K_BEV_SCAN, PCA_K_BEV_SCATTER, PCA_K_BEV_CELLS, PCA_K_BEV_CELLS_HEAVY, PCA_K_DEDUP, PCA_K_BEV_UNIT, PCA_K_ICP,
     PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS,
-    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_RENDER_ZBUFFER, PCA_K_RENDER_RESOLVE, PCA_K_COUNT
+    PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_RENDER_ZBUFFER, PCA_K_RENDER_RESOLVE,
+    PCA_K_BEV_CARVE_ENDS, PCA_K_BEV_CARVE_RAYS, PCA_K_BEV_CARVE_FLAGS, PCA_K_COUNT
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

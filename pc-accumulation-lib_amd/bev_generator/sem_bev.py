@@ -238,8 +238,8 @@ class SemBEVGenerator(BEVGenerator):
                 raise ValueError(f"sem_planes: '{name}' is the name of one of the sample's own planes")
         return list(planes), [self._classes_of(v) for v in planes.values()]
 
-    # ---- one point set, one read-only pass: what class_planes_device, elev_partition_device, voxel_labels_device and
-    #      voxel_rays_device share (a new pass of this family plugs in here and in DeviceStore._window_pass) ----
+    # ---- one point set, one read-only pass: what class_planes_device, elev_partition_device, voxel_labels_device,
+    #      voxel_rays_device and voxel_carve_device share (a new pass of this family plugs in here and in DeviceStore._window_pass) ----
     def _pass_params(self, pc, rot_mat, dx, dy, aug_view_size):
         """pca_bev_params of a pass over `pc`: a WindowPart brings its window's origin, host rows are in BEV-frame metres."""
         if isinstance(pc, WindowPart):
@@ -379,6 +379,31 @@ class SemBEVGenerator(BEVGenerator):
             pc = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in pc]
         st, prm, frames = self._one_set_pass(pc, 'rays', rot_mat, dx, dy, aug_view_size, per_frame=True)
         return st.bev_voxel_rays(prm, *grid, origins, include_dyn=include_dyn, **frames)
+
+    # ---- free-space carving: points that beams saw through are dynamic (extension: pca_bev_voxel_carve) ------------
+    def dynamic_classes(self):
+        """The classes that can move: sem_idxs' car, truck, bus and motorcycle (those the dynamic plane is made of)."""
+        return [self.sem_idxs[k] for k in ('car', 'truck', 'bus', 'motorcycle') if k in self.sem_idxs]
+
+    def voxel_carve_device(self, pc, origins, rot_mat, dx, dy, aug_view_size, z_range, nz, classes=None, end_margin=1,
+                           min_cross=2, ratio=1.0, include_dyn=False, mark_dyn=False):
+        """The rays of voxel_rays_device (same point sets, same origins, same grid), counted: DeviceStore.bev_voxel_carve's
+        dict of cuda tensors 'hits', 'cross' (int32 [nz, px, px]), 'flags' (uint8, one per point: 1 = a point of `classes`
+        whose voxel the beams went through, 0 = one they did not, 255 everything else) and 'stats' (int64 [6]).  classes:
+        class indices or sem_idxs names; None: dynamic_classes().  The defaults of end_margin, min_cross and ratio are this
+        project's choice, checked on a synthetic scene only; no real-data number exists.
+        mark_dyn applies to a WindowPart only: the flagged points of the device window get dyn = 1, for good."""
+        grid = self._voxel_grid(z_range, nz)
+        if isinstance(pc, np.ndarray):
+            raise ValueError('voxel_carve_device: host rows come as a list of per-frame arrays, one origin each')
+        if mark_dyn and not isinstance(pc, WindowPart):
+            raise ValueError('mark_dyn needs a device window: host rows are not written')
+        if not isinstance(pc, WindowPart):
+            pc = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in pc]
+        classes = self.dynamic_classes() if classes is None else self._classes_of(classes)
+        st, prm, frames = self._one_set_pass(pc, 'carve', rot_mat, dx, dy, aug_view_size, per_frame=True)
+        return st.bev_voxel_carve(prm, *grid, origins, classes, end_margin=end_margin, min_cross=min_cross, ratio=ratio,
+                                  include_dyn=include_dyn, mark_dyn=mark_dyn, **frames)
 
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the

@@ -15,12 +15,13 @@
 //                    against 1.62 on the headline window; ALWAYS_STORE, every mark a store without the load: 1.69 ms --
 //                    profiles/bev_voxel_rays.txt).  A ray leaves its loop early only by integer tests that cannot change
 //                    the marked set.  The four counters: per lane, per wave, LDS, one global add per counter and workgroup.
-// The store is never written.  PCA_BEV_RAYS_MAX_STEPS bounds every ray, hence every launch.
-#include "pca_bev_view.h"
+// The store is never written.  PCA_BEV_RAYS_MAX_STEPS bounds every ray, hence every launch.  The grid coordinates and the
+// ray's set-up (voxels, step counts, tMax, tDelta) come from pca_bev_ray_setup.h, shared with pca_bev_carve.hip; the step
+// loop below stays written out here, as it was tuned.
+#include "pca_bev_ray_setup.h"
 
 #define RAY_THREADS 256
 #define RAY_MAX_G 2048            // workgroups at most (eight per CU; the registers let six of them be resident)
-#define RAY_COORD_LIM 1073741824.0   // 2^30: a grid coordinate at or above it in magnitude drops the ray
 
 struct alignas(16) RayArgs {
     pca_store st;
@@ -38,19 +39,6 @@ struct alignas(16) RayArgs {
     uint32_t *status;             // context status word (PCA_STATUS_* bits)
 };
 
-struct RayGrid { double ox, oy, oz, r0, r1, r3, r4, dx, dy, view, pxd, half_px, z_lo, z_step; };
-// grid coordinates of a position: each operation rounded on its own (-ffp-contract=off), the sums unfused
-__device__ __forceinline__ void ray_coords(const RayGrid &q, double X, double Y, double Z, double &u, double &v, double &w)
-{
-    const double x = X - q.ox, y = Y - q.oy;
-    const double ax = (q.r0 * x + q.r1 * y) + q.dx;
-    const double ay = (q.r3 * x + q.r4 * y) + q.dy;
-    u = ax / q.view * q.pxd + q.half_px;
-    v = ay / q.view * q.pxd + q.half_px;
-    w = (((Z - q.oz) + 0.0) - q.z_lo) / q.z_step;
-}
-__device__ __forceinline__ bool ray_coord_ok(double t) { return fabs(t) < RAY_COORD_LIM; }   // (false for NaN)
-
 template <bool ALWAYS_STORE>
 __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
 {
@@ -64,12 +52,7 @@ __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
     if (hi > a.st.capacity) hi = a.st.capacity;            // (nothing is stored behind the capacity, whatever frame_off counts)
     if (blockIdx.x == 0 && tid == 0 && hi0 - lo > a.max_points) pca_raise(a.status, PCA_STATUS_STORE_OVERFLOW);
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
-    RayGrid q;
-    q.ox = a.prm.origin[0]; q.oy = a.prm.origin[1]; q.oz = a.prm.origin[2];
-    q.r0 = a.prm.R[0]; q.r1 = a.prm.R[1]; q.r3 = a.prm.R[3]; q.r4 = a.prm.R[4];
-    q.dx = a.prm.dx; q.dy = a.prm.dy; q.view = a.prm.view;
-    q.pxd = (double)a.prm.px; q.half_px = 0.5 * q.pxd;
-    q.z_lo = a.z_lo; q.z_step = a.z_step;
+    const RayGrid q = ray_grid(a.prm, a.z_lo, a.z_step);
     const int px = a.prm.px, nz = a.nz;
     auto *seen = reinterpret_cast<__attribute__((address_space(1))) uint8_t *>(reinterpret_cast<uintptr_t>(a.seen));
     const double INF = __builtin_huge_val();
@@ -99,10 +82,10 @@ __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
             ++n_not_finite;
             continue;
         }
-        int c0 = (int)floor(s0), c1 = (int)floor(s1), c2 = (int)floor(s2);
-        const int g0 = (int)floor(e0), g1 = (int)floor(e1), g2 = (int)floor(e2);
-        int n0 = abs(g0 - c0), n1 = abs(g1 - c1), n2 = abs(g2 - c2);           // (each below 2^31: |c|, |g| <= 2^30)
-        const int64_t N64 = (int64_t)n0 + n1 + n2;
+        const RayVoxels r = ray_voxels(s0, s1, s2, e0, e1, e2);
+        int c0 = r.c0, c1 = r.c1, c2 = r.c2, n0 = r.n0, n1 = r.n1, n2 = r.n2;
+        const int g0 = r.g0, g1 = r.g1, g2 = r.g2;
+        const int64_t N64 = ray_steps(r);
         if (N64 > PCA_BEV_RAYS_MAX_STEPS) {
             ++n_too_long;
             continue;
@@ -112,12 +95,10 @@ __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
         if (!a.seen || (c0 < 0 && g0 < 0) || (c0 >= px && g0 >= px) || (c1 < 0 && g1 < 0) || (c1 >= px && g1 >= px) ||
             (c2 < 0 && g2 < 0) || (c2 >= nz && g2 >= nz))
             continue;
-        const int st0 = (g0 > c0) - (g0 < c0), st1 = (g1 > c1) - (g1 < c1), st2 = (g2 > c2) - (g2 < c2);
-        const double d0 = e0 - s0, d1 = e1 - s1, d2 = e2 - s2;
-        double t0 = INF, t1 = INF, t2 = INF, dl0 = 0.0, dl1 = 0.0, dl2 = 0.0;
-        if (n0 > 0) { t0 = ((double)(c0 + (st0 > 0 ? 1 : 0)) - s0) / d0; dl0 = 1.0 / fabs(d0); }
-        if (n1 > 0) { t1 = ((double)(c1 + (st1 > 0 ? 1 : 0)) - s1) / d1; dl1 = 1.0 / fabs(d1); }
-        if (n2 > 0) { t2 = ((double)(c2 + (st2 > 0 ? 1 : 0)) - s2) / d2; dl2 = 1.0 / fabs(d2); }
+        const RayMarch m0 = ray_march(r, s0, s1, s2, e0, e1, e2);
+        const int st0 = m0.st0, st1 = m0.st1, st2 = m0.st2;
+        const double dl0 = m0.dl0, dl1 = m0.dl1, dl2 = m0.dl2;
+        double t0 = m0.t0, t1 = m0.t1, t2 = m0.t2;
         const int N = (int)N64;
         // a mark's byte is looked at one step later (pm, pv: the byte of the step before and what the load gave), so that the
         // load's round trip runs beside a whole step's arithmetic; pv = 1: nothing waits

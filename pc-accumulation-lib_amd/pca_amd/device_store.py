@@ -598,7 +598,8 @@ class DeviceStore:
         self._k1_noted = None                      # (a raster takes a noted K1 along or runs it first: nothing is noted any more)
 
     def _side_workspace(self, name, workspace_bytes, max_points, px):
-        """The scratch of a side pass (bev_class_planes, bev_elev_partition, bev_voxel_labels), fit for max_points at `px`."""
+        """The scratch of a side pass (bev_class_planes, bev_elev_partition, bev_voxel_labels, bev_voxel_carve), fit for
+        max_points at `px`."""
         ws = self._ws_side.setdefault(name, [None, 0, 0])
         if ws[0] is None or max_points > ws[1] or px != ws[2]:
             # sized with headroom so that a window growing frame by frame does not reallocate every call
@@ -610,7 +611,7 @@ class DeviceStore:
 
     def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None):
         """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
-        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, render_camera -- whose `prm` is its camera block; the next pass
+        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, render_camera -- whose `prm` is its camera block; the next pass
         of the family starts here): last_frame's default,
         the bound at which the window is cut (max_points; default: the live window's own) and -- side = (name,
         pca_*_workspace_bytes) -- the pass's scratch.  Returns (last_frame, max_points, call).
@@ -724,20 +725,71 @@ class DeviceStore:
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
         last_frame, max_points, call = self._window_pass(prm, first_frame, last_frame, max_points)
         px = int(prm.px)
+        org = self._origins_of(origins, last_frame - first_frame)
+        shape = (max(int(nz), 1), max(px, 1), max(px, 1))
+        seen = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(4, dtype=torch.int64, device=self.device)
+        call(self.ctx.lib.pca_bev_voxel_rays, (float(z_lo), float(z_step), int(nz), 1 if include_dyn else 0, org.data_ptr()),
+             (seen, stats))
+        return {'seen': seen, 'stats': stats}
+
+    def _origins_of(self, origins, n_frames):
+        """origins [n_frames, 3] (numpy or tensor) as an f64 device tensor; a valid pointer even for no frame."""
         if isinstance(origins, torch.Tensor):
             org = origins.to(device=self.device, dtype=torch.float64).contiguous()
         else:
             org = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64)).to(self.device)
-        if org.dim() != 2 or org.shape[1] != 3 or org.shape[0] != last_frame - first_frame:
+        if org.dim() != 2 or org.shape[1] != 3 or org.shape[0] != n_frames:
             raise ValueError('origins must be [frames, 3], one row per frame of the range')
-        shape = (max(int(nz), 1), max(px, 1), max(px, 1))
-        seen = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        stats = torch.empty(4, dtype=torch.int64, device=self.device)
         if org.shape[0] == 0:
-            org = torch.zeros((1, 3), dtype=torch.float64, device=self.device)     # (never read: a valid pointer)
-        call(self.ctx.lib.pca_bev_voxel_rays, (float(z_lo), float(z_step), int(nz), 1 if include_dyn else 0, org.data_ptr()),
-             (seen, stats))
-        return {'seen': seen, 'stats': stats}
+            org = torch.zeros((1, 3), dtype=torch.float64, device=self.device)     # (never read)
+        return org
+
+    def bev_voxel_carve(self, prm, z_lo, z_step, nz, origins, classes, end_margin=1, min_cross=2, ratio=1.0, first_frame=0,
+                        last_frame=None, include_dyn=False, mark_dyn=False, max_points=None):
+        """Free-space carving by ray hit / miss over the live frames [first_frame, last_frame) (pca_bev_voxel_carve): the
+        rays of bev_voxel_rays (same grid, same origins, same drop rules), counted.  Per voxel, 'hits' = the rays that end in
+        it and 'cross' = the rays that pass through it at a step more than end_margin steps before their own end -- counted
+        only for CANDIDATE voxels, those in which a point of `classes` (a list of class indices: the classes that can move)
+        ends; 0 elsewhere.  A candidate point is FLAGGED iff cross >= min_cross and cross >= ratio * hits in its voxel: beams
+        of other moments went straight through where it was seen, so it belonged to something that moved.  The rays of a
+        point's own frame count like any other: end_margin keeps a surface from carving itself, ratio keeps a surface that is
+        hit as often as it is crossed.  include_dyn=False: points with dyn == 1 take no part.
+        The defaults (1, 2, 1.0) are this project's choice, checked on a synthetic scene only (tests/test_voxel_carve_model.py:
+        a car that leaves is flagged whole, a parked one not at all); no real-data number exists.
+        Returns a dict of cuda tensors: 'hits' and 'cross' int32 [nz, px, px] holding the u32 counts, image rows; 'flags'
+        uint8, one per point of the window in store order (1 flagged, 0 candidate kept, 255 everything else; the window's
+        exact length: one offset is read back, the call synchronises); 'stats' int64 [6]: points that take part, rays cast,
+        dropped not finite, dropped too long, candidate points, flagged points.
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed -- unless mark_dyn=True,
+        the only path that alters the store: the flagged points get dyn = 1, for good (owed re-transforms are flushed first).
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        lib = self.ctx.lib
+        if not 0 <= int(min_cross) < 1 << 32 or not -(1 << 31) <= int(end_margin) < 1 << 31:
+            raise ValueError('min_cross must fit an unsigned, end_margin a signed 32-bit integer')
+        if mark_dyn:
+            self.flush_pending()                       # a call that must write: nothing stays owed
+        nz = int(nz)
+        last_frame, max_points, call = self._window_pass(
+            prm, first_frame, last_frame, max_points,
+            side=('carve', lambda m, px: lib.pca_bev_carve_workspace_bytes(m, px, nz)))
+        org = self._origins_of(origins, last_frame - first_frame)
+        only = _lib.PcaClassGroup()
+        only.mask[:] = list(_lib.class_mask(classes))
+        px = int(prm.px)
+        shape = (max(nz, 1), max(px, 1), max(px, 1))
+        hits = torch.empty(shape, dtype=torch.int32, device=self.device)
+        cross = torch.empty(shape, dtype=torch.int32, device=self.device)
+        flags = torch.empty(max_points, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(6, dtype=torch.int64, device=self.device)
+        call(lib.pca_bev_voxel_carve, (float(z_lo), float(z_step), nz, 1 if include_dyn else 0, org.data_ptr(), only,
+                                       int(end_margin), int(min_cross), float(ratio)), (hits, cross, flags, stats))
+        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
+        lo, n = int(lo_hi[0]), min(int(lo_hi[1] - lo_hi[0]), max_points)
+        flags = flags[:n]
+        if mark_dyn:
+            self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
+        return {'hits': hits, 'cross': cross, 'flags': flags, 'stats': stats}
 
     def render_camera(self, cam, first_frame=0, last_frame=None, classes=None, max_points=None):
         """The stored points of the live frames [first_frame, last_frame) rendered into a pinhole camera with a z-buffer

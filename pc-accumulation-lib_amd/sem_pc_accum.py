@@ -380,6 +380,32 @@ class SemanticPointCloudAccumulator:
         out['state'] = torch.where(out['counts'] != 0, 2, out['seen'].to(torch.int32)).to(torch.uint8)
         return out
 
+    def carve_dynamic(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, end_margin=1, min_cross=2,
+                      ratio=1.0, origins=None, mark_dyn=False):
+        """Extension (no reference counterpart): free-space carving by ray hit / miss over `part` ('present' | 'future' |
+        'full') of the sample generate_bev(present_idx, 1, True) would make, in that sample's un-augmented frame, on the grid
+        of voxel_occupancy.  A voxel in which a point of `classes` was seen at one moment, and which the beams of other
+        frames later passed straight through, held a moving object: a point of `classes` is FLAGGED iff its voxel was crossed
+        by at least min_cross rays, and by at least ratio times as many rays as ended in it; a ray's last end_margin steps
+        before its own end voxel do not count, which keeps a surface from carving itself.  What KITTI needs, where no
+        instance labels exist and dyn is 0 everywhere -- and, unlike partition_by_elev, it tells a parked car from a moving
+        one and leaves poles and walls alone.
+        classes: class indices or sem_idxs names; None: the generator's dynamic classes (car, truck, bus, motorcycle).
+        origins: as voxel_occupancy takes them; None: the pose-track rows of the part's frames.  One origin per stored frame.
+        The defaults (end_margin=1, min_cross=2, ratio=1.0) are this project's choice, checked only on a synthetic scene (a
+        wall, a parked car and a car that leaves: tests/test_voxel_carve_model.py); no real-data number exists.
+        Returns DeviceStore.bev_voxel_carve's dict of cuda tensors 'hits', 'cross', 'flags', 'stats'.  Points with dyn == 1
+        take no part.  Nothing is written -- unless mark_dyn=True: the flagged points get dyn = 1 in the store, for good (owed
+        re-transforms are flushed first), and stay out of the static planes of every later sample.  integrate() never calls
+        this on its own."""
+        gen = self.sem_bev_generator
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        if origins is None:
+            lo, hi = pc.frames()
+            origins = self._track.as_array()[lo:hi]
+        return gen.voxel_carve_device(pc, origins, rot_mat, 0., 0., view, z_range, nz, classes=classes, end_margin=end_margin,
+                                      min_cross=min_cross, ratio=ratio, include_dyn=False, mark_dyn=mark_dyn)
+
     def _render_defaults(self):
         """(P, (W, H)) of render_camera where the dataset has one camera the stored coordinates belong to; (None, None) here."""
         return None, None
