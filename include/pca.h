@@ -573,6 +573,66 @@ int pca_bev_voxel_carve(pca_ctx *ctx, const pca_store *store, const int64_t *fra
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The object voxels of the window clustered into instances: Euclidean clustering on the voxel grid of pca_bev_voxel_labels,
+ *       that is connected-component labelling of its occupied voxels, a deterministic numbering of the components, and the
+ *       instance of every stored point.  No reference counterpart.  What KITTI needs to say which points form one object
+ *       (panoptic occupancy ground truth, per-object boxes and counts, a carved mover treated as one thing).
+ *     Geometry and kept points are word for word those of pca_bev_voxel_labels, from the same code: owed re-transforms
+ *       oldest first, origin, R about z, dx / dy, strict crop, z < height_filter, floor, clamp, image rows; the f64 height
+ *       bin with the IEEE division, nothing clamped in z; a point whose label_of[class] is 255 takes no part.  counts[v]
+ *       below IS pca_bev_voxel_labels' counts for the same label table and the same dyn rule.
+ *     dyn_mode 0: points with dyn == 1 take no part; 1: every point takes part; 2: ONLY points with dyn == 1 take part (the
+ *       movers after a carve that marked them, or of a NuScenes window).
+ *     Foreground: voxel v is foreground iff counts[v] >= min_points (min_points >= 1).
+ *     Neighbours, on the output index (k, row, col), place = (k px + row) px + col: connectivity 6 -- exactly one coordinate
+ *       differs, by 1; connectivity 26 -- no coordinate differs by more than 1 and not all are equal.  Nothing wraps:
+ *       (k, row, px - 1) and (k, row + 1, 0) are adjacent places and NOT neighbours, nor are the last row of a height plane
+ *       and the first row of the next.
+ *     A component is a maximal connected set of foreground voxels; its root is its smallest place; it SURVIVES iff it has at
+ *       least min_voxels voxels (min_voxels >= 1).  The n surviving components are numbered 0 .. n - 1 in ascending order
+ *       of their roots: the numbering is a function of the kept points as a set, not of their order or of any scheduling.
+ *     Output (dev, any of them may be NULL, not all; each is cleared or fully written by the call itself, on the stream):
+ *       inst i32 [nz][px][px]: the id of the surviving component that holds the voxel, else -1;
+ *       ids i32 [window points], window order: inst of the voxel of a kept point, -1 for every other point (every entry of the
+ *         cut window is written exactly once, nothing behind the cut is written); neither inst nor ids is capped by
+ *         max_instances;
+ *       table u32 [max_instances][PCA_BEV_INST_COLS], row id < min(n, max_instances): root place, voxels, kept points,
+ *         col_min, col_max, row_min, row_max, k_min, k_max; the rows from n on are zero;
+ *       label_counts u32 [max_instances][n_labels]: the kept points of label l in instance id;
+ *       stats i64 [6]: kept points, foreground voxels, components, surviving components (n), kept points with ids >= 0,
+ *         voxels of the largest surviving component.
+ *       All sums are integer sums and all extremes integer extremes: exact and free of any order.
+ *     Scope: the boxes are VOXEL boxes; a metric box tighter than the voxels is not computed (pca_amd.host_logic.instance_boxes
+ *       turns the voxel box into metres).  No automatic call from integrate().
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32, 1 <= n_labels <= 32, connectivity 6 or 26, 1 <= max_instances <= 65536,
+ *       max_points < 2^31, z_lo finite, z_step finite and > 0, dyn_mode 0..2, min_points >= 1, min_voxels >= 1, a workspace
+ *       of pca_bev_instances_workspace_bytes(max_points, px, nz, max_instances) bytes.
+ *     The call enqueues a fixed number of launches and never waits for the device; no kernel waits for another workgroup.
+ *     The store is never written: owed re-transforms (pending_Ts / pending_slot_ends / n_pending as pca_bev_generate_chain
+ *     takes them) are applied to the points that are read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a
+ *     bin range armed by pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared.  A window above max_points is
+ *     cut there and raises PCA_STATUS_STORE_OVERFLOW; a window without points gives inst -1, stats 0, zero tables and writes
+ *     no ids.  Every argument is checked before anything is launched; -1 with pca_last_error set ("bev voxel instances:
+ *     ..."), nothing written.
+ * ------------------------------------------------------------------------------------------------ */
+#define PCA_BEV_INST_COLS 9
+int64_t pca_bev_instances_workspace_bytes(int64_t max_points, int px, int nz, int max_instances);
+int pca_bev_voxel_instances(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                            int slot_begin, int slot_end, int64_t max_points,
+                            const pca_bev_params *prm, double z_lo, double z_step, int nz,
+                            const uint8_t label_of[256] /*host*/, int n_labels, int dyn_mode,
+                            int min_points, int connectivity, int min_voxels, int max_instances,
+                            const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                            void *workspace /*dev*/, int64_t workspace_bytes,
+                            int32_t  *inst         /*dev [nz][px][px] or NULL*/,
+                            int32_t  *ids          /*dev [window points] or NULL*/,
+                            uint32_t *table        /*dev [max_instances][PCA_BEV_INST_COLS] or NULL*/,
+                            uint32_t *label_counts /*dev [max_instances][n_labels] or NULL*/,
+                            int64_t  *stats        /*dev [6] or NULL*/,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The window of the store rendered into a pinhole camera with a z-buffer: dense depth, colour and class targets for an
  *       image (what KITTI depth completion calls accumulated lidar ground truth).  The projection and its mask are the
  *       reference's velo2frame + velo2img, sem_pc_accum.py:347-402, on the stored f64 coordinates (owed re-transforms
@@ -952,6 +1012,11 @@ enum {
     PCA_K_BEV_CLASS_BIN, PCA_K_BEV_CLASS_CELLS, PCA_K_BEV_ELEV_BIN, PCA_K_BEV_ELEV_CELLS,
     PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_RENDER_ZBUFFER, PCA_K_RENDER_RESOLVE,
     PCA_K_BEV_CARVE_ENDS, PCA_K_BEV_CARVE_RAYS, PCA_K_BEV_CARVE_FLAGS, PCA_K_COUNT
+};
+/* The ids that follow (the first block above is closed: its length is pinned): the kernels of pca_bev_voxel_instances. */
+enum {
+    PCA_K_BEV_INST_INIT = PCA_K_COUNT, PCA_K_BEV_INST_MERGE, PCA_K_BEV_INST_COMPRESS, PCA_K_BEV_INST_SUMS, PCA_K_BEV_INST_OFFSETS,
+    PCA_K_BEV_INST_NUMBER, PCA_K_BEV_INST_WRITE, PCA_K_BEV_INST_POINTS, PCA_K_TOTAL
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

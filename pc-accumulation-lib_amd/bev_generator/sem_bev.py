@@ -239,7 +239,7 @@ class SemBEVGenerator(BEVGenerator):
         return list(planes), [self._classes_of(v) for v in planes.values()]
 
     # ---- one point set, one read-only pass: what class_planes_device, elev_partition_device, voxel_labels_device,
-    #      voxel_rays_device and voxel_carve_device share (a new pass of this family plugs in here and in DeviceStore._window_pass) ----
+    #      voxel_rays_device, voxel_carve_device and voxel_instances_device share (a new pass of this family plugs in here and in DeviceStore._window_pass) ----
     def _pass_params(self, pc, rot_mat, dx, dy, aug_view_size):
         """pca_bev_params of a pass over `pc`: a WindowPart brings its window's origin, host rows are in BEV-frame metres."""
         if isinstance(pc, WindowPart):
@@ -404,6 +404,21 @@ class SemBEVGenerator(BEVGenerator):
         st, prm, frames = self._one_set_pass(pc, 'carve', rot_mat, dx, dy, aug_view_size, per_frame=True)
         return st.bev_voxel_carve(prm, *grid, origins, classes, end_margin=end_margin, min_cross=min_cross, ratio=ratio,
                                   include_dyn=include_dyn, mark_dyn=mark_dyn, **frames)
+
+    # ---- object voxels clustered into instances (extension: pca_bev_voxel_instances) ------------
+    def voxel_instances_device(self, pc, rot_mat, dx, dy, aug_view_size, z_range, nz, classes=None, min_points=1,
+                               connectivity=26, min_voxels=1, max_instances=4096, dyn='static'):
+        """One point set clustered into instances on the grid of voxel_labels_device (same frame, same z_range and nz):
+        DeviceStore.bev_voxel_instances' dict of cuda tensors 'inst', 'ids', 'table', 'label_counts', 'top_label', 'stats'.
+        pc: a WindowPart ('ids' in the order of the part's frames in the store) or host rows in BEV-frame metres ('ids' in
+        row order).  classes: a list of class lists as voxel_labels_device takes them, list i becomes label i (sem_idxs
+        names are taken too) and every other class takes no part; None: dynamic_classes(), one label each."""
+        grid = self._voxel_grid(z_range, nz)
+        classes = [[c] for c in self.dynamic_classes()] if classes is None else [self._classes_of(g) for g in classes]
+        table, n_labels = self.voxel_label_table(classes)
+        st, prm, frames = self._one_set_pass(pc, 'inst', rot_mat, dx, dy, aug_view_size)
+        return st.bev_voxel_instances(prm, *grid, table, n_labels, min_points=min_points, connectivity=connectivity,
+                                      min_voxels=min_voxels, max_instances=max_instances, dyn=dyn, **frames)
 
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the

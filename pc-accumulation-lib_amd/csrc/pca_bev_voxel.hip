@@ -15,23 +15,12 @@
 //                              is re-read from L2 (2 B each) once per slab: counts, barrier, argmax per voxel (the cell
 //                              fastest: conflict-free LDS reads, eight lanes write one tile row).
 // The order in which a tile's records arrive is not fixed (LDS cursors); counts and their argmax do not depend on it.
-#include "pca_bev_side.h"
+#include "pca_bev_voxel.h"
 
 #define VB_REG_P 12               // points per thread of level 1 whose key stays in registers between its passes
 #define VC_THREADS SIDE_CELLS_THREADS
 #define VC_REG_R 16               // records per thread of level 2 that stay in registers between the slabs
 #define VC_SLAB_COUNTERS 14336    // u32 counters of a slab at most: 56 KiB, which with side_tile_runs' tables stays below 64 KiB
-
-struct alignas(16) VoxArgs {
-    SideArgs s;                   // (slot_split = slot_begin: the voxels know no sets)
-    double z_lo, z_step;
-    int nz, n_labels, include_dyn;
-    int zs;                       // height bins per slab of level 2
-    uint16_t *recs;               // [max_points + G]: cell_in_tile << 10 | k << 5 | label, tile-ordered per segment
-    uint8_t *labels;              // [nz][px][px] or NULL
-    uint32_t *counts, *top;       // [nz][px][px] or NULL
-    uint8_t label_of[256];        // class -> label, 255: the class takes no part
-};
 
 // ---------------------------------------------------------------------------------------------
 // level 1
@@ -41,19 +30,10 @@ struct VoxBin {
     struct Payload {};
     const VoxArgs &v;
     const uint8_t *label_of;      // the table in LDS: the lookup hangs on the class word's load, a second trip to memory would show
-    // key of stored point p: the view's key (tile << 7 | cell_in_tile << 1 | set, set = 0) >> 1, then k and the label
-    __device__ __forceinline__ uint32_t key(const SideArgs &a, const ViewConst &vc, const PendHi &pend_hi, const SideWindow &, int64_t p, Payload &) const
+    // key of stored point p: pca_bev_voxel.h's
+    __device__ __forceinline__ uint32_t key(const SideArgs &, const ViewConst &vc, const PendHi &pend_hi, const SideWindow &, int64_t p, Payload &) const
     {
-        double X = pca_ldg(a.st.x + p), Y = pca_ldg(a.st.y + p), Z = pca_ldg(a.st.z + p);
-        const uint8_t D = pca_ldg(a.st.dyn + p);
-        apply_owed(a.owed, pend_hi, p, X, Y, Z);
-        const uint32_t vk = view_key_lean<false>(vc, X, Y, Z, v.include_dyn != 0 || D != 1, 0u);
-        if (vk == KEY_INVALID) return KEY_INVALID;
-        const uint32_t label = label_of[pca_ldg(a.st.rgbs + p) >> 24];    // (the class byte: read for the kept points only)
-        const double z = (Z - vc.oz) + 0.0;
-        const double kf = floor((z - v.z_lo) / v.z_step);       // the IEEE division: no reciprocal, nothing fused
-        if (label == 255u || !(kf >= 0.0 && kf < (double)v.nz)) return KEY_INVALID;   // in z nothing is clamped
-        return ((vk >> 1) << 10) | ((uint32_t)(int)kf << 5) | label;
+        return vox_point_key(v, vc, pend_hi, p, label_of);
     }
     __device__ __forceinline__ void dropped(const SideWindow &, int64_t) const {}
     __device__ __forceinline__ void store(int g, const SideWindow &w, uint32_t pos, uint32_t key, const Payload &, int64_t) const
@@ -139,9 +119,49 @@ __global__ __launch_bounds__(VC_THREADS) void bev_voxel_cells(const VoxArgs a)
 static SideLayout vox_layout(int64_t max_points, int px) { return side_layout(max_points, px, 2, 0, "PCA_BEV_VOXEL_G"); }
 static const WindowPass VOX_PASS = {"bev voxel labels", true, false};
 
+int64_t bev_voxel_workspace(int64_t max_points, int px) { return vox_layout(max_points, px).total; }
+
+int bev_voxel_prepare(pca_ctx *ctx, const WindowPass &pass, bool own_ok, const pca_store *store, const int64_t *frame_off,
+                      int slot_begin, int slot_end, int64_t max_points, const pca_bev_params *prm, double z_lo, double z_step,
+                      int nz, const uint8_t *label_of, int n_labels, int dyn_mode, const double *pending_Ts,
+                      const int *pending_slot_ends, int n_pending, void *workspace, int64_t workspace_bytes, VoxArgs &A)
+{
+    const std::string what(pass.what);
+    char *w;
+    if (window_check(ctx, pass, label_of && workspace && own_ok, store, frame_off, slot_begin, slot_begin, slot_end, max_points,
+                     prm, pending_Ts, pending_slot_ends, n_pending, A.s))
+        return -1;
+    if (voxel_grid_check(ctx, pass.what, z_lo, z_step, nz)) return -1;
+    if (n_labels < 1 || n_labels > PCA_BEV_VOXEL_MAX_LABELS) { ctx->err = what + ": n_labels must be in 1..32"; return -1; }
+    for (int c = 0; c < 256; ++c)
+        if (label_of[c] != 255 && label_of[c] >= n_labels) {
+            ctx->err = what + ": label_of[" + std::to_string(c) + "] must be below n_labels, or 255";
+            return -1;
+        }
+    if (side_tiles(ctx, pass.what, slot_begin, workspace, workspace_bytes, vox_layout(max_points, prm->px), A.s, w)) return -1;
+    A.z_lo = z_lo; A.z_step = z_step;
+    A.nz = nz; A.n_labels = n_labels; A.dyn_mode = dyn_mode;
+    // the slabs of level 2: as few as the counters allow, then of equal height
+    const int zs_max = VC_SLAB_COUNTERS / (TCELLS * n_labels);
+    const int n_slabs = (nz + zs_max - 1) / zs_max;
+    A.zs = (nz + n_slabs - 1) / n_slabs;
+    A.recs = reinterpret_cast<uint16_t *>(w);
+    A.labels = nullptr; A.counts = nullptr; A.top = nullptr;
+    for (int c = 0; c < 256; ++c) A.label_of[c] = label_of[c];
+    return 0;
+}
+
+int bev_voxel_enqueue(pca_ctx *ctx, const VoxArgs &args, hipStream_t s)
+{
+    if (side_launch_bin<bev_voxel_bin>(ctx, PCA_K_BEV_VOXEL_BIN, args, s)) return -1;
+    PCA_LAUNCH_SHM(ctx, PCA_K_BEV_VOXEL_CELLS, bev_voxel_cells, dim3(args.s.T), dim3(VC_THREADS),
+                   (size_t)args.zs * args.n_labels * TCELLS * 4, s, args);
+    return 0;
+}
+
 extern "C" {
 
-int64_t pca_bev_voxel_workspace_bytes(int64_t max_points, int px) { return vox_layout(max_points, px).total; }
+int64_t pca_bev_voxel_workspace_bytes(int64_t max_points, int px) { return bev_voxel_workspace(max_points, px); }
 
 int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off, int slot_begin, int slot_end,
                          int64_t max_points, const pca_bev_params *prm, double z_lo, double z_step, int nz,
@@ -151,34 +171,14 @@ int pca_bev_voxel_labels(pca_ctx *ctx, const pca_store *store, const int64_t *fr
 {
     if (!ctx) return -1;
     if (max_points < 1) max_points = 1;
-    hipStream_t s = (hipStream_t)stream;
     // every check comes before the first launch (a noted K1 included)
     VoxArgs A;
-    char *w;
-    if (window_check(ctx, VOX_PASS, label_of && workspace && (labels || counts || top), store, frame_off, slot_begin, slot_begin,
-                     slot_end, max_points, prm, pending_Ts, pending_slot_ends, n_pending, A.s))
+    if (bev_voxel_prepare(ctx, VOX_PASS, labels || counts || top, store, frame_off, slot_begin, slot_end, max_points, prm, z_lo,
+                          z_step, nz, label_of, n_labels, include_dyn != 0 ? 1 : 0, pending_Ts, pending_slot_ends, n_pending,
+                          workspace, workspace_bytes, A))
         return -1;
-    if (voxel_grid_check(ctx, VOX_PASS.what, z_lo, z_step, nz)) return -1;
-    if (n_labels < 1 || n_labels > PCA_BEV_VOXEL_MAX_LABELS) { ctx->err = "bev voxel labels: n_labels must be in 1..32"; return -1; }
-    for (int c = 0; c < 256; ++c)
-        if (label_of[c] != 255 && label_of[c] >= n_labels) {
-            ctx->err = "bev voxel labels: label_of[" + std::to_string(c) + "] must be below n_labels, or 255";
-            return -1;
-        }
-    if (side_tiles(ctx, VOX_PASS.what, slot_begin, workspace, workspace_bytes, vox_layout(max_points, prm->px), A.s, w)) return -1;
-    A.z_lo = z_lo; A.z_step = z_step;
-    A.nz = nz; A.n_labels = n_labels; A.include_dyn = include_dyn;
-    // the slabs of level 2: as few as the counters allow, then of equal height
-    const int zs_max = VC_SLAB_COUNTERS / (TCELLS * n_labels);
-    const int n_slabs = (nz + zs_max - 1) / zs_max;
-    A.zs = (nz + n_slabs - 1) / n_slabs;
-    A.recs = reinterpret_cast<uint16_t *>(w);
     A.labels = labels; A.counts = counts; A.top = top;
-    for (int c = 0; c < 256; ++c) A.label_of[c] = label_of[c];
-    const VoxArgs &args = A;
-    if (side_launch_bin<bev_voxel_bin>(ctx, PCA_K_BEV_VOXEL_BIN, args, s)) return -1;
-    PCA_LAUNCH_SHM(ctx, PCA_K_BEV_VOXEL_CELLS, bev_voxel_cells, dim3(args.s.T), dim3(VC_THREADS),
-                   (size_t)args.zs * n_labels * TCELLS * 4, s, args);
+    if (bev_voxel_enqueue(ctx, A, (hipStream_t)stream)) return -1;
     PCA_CHECK(ctx, hipGetLastError());
     return 0;
 }

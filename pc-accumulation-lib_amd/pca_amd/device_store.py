@@ -598,7 +598,7 @@ class DeviceStore:
         self._k1_noted = None                      # (a raster takes a noted K1 along or runs it first: nothing is noted any more)
 
     def _side_workspace(self, name, workspace_bytes, max_points, px):
-        """The scratch of a side pass (bev_class_planes, bev_elev_partition, bev_voxel_labels, bev_voxel_carve), fit for
+        """The scratch of a side pass (bev_class_planes, bev_elev_partition, bev_voxel_labels, bev_voxel_carve, bev_voxel_instances), fit for
         max_points at `px`."""
         ws = self._ws_side.setdefault(name, [None, 0, 0])
         if ws[0] is None or max_points > ws[1] or px != ws[2]:
@@ -611,7 +611,7 @@ class DeviceStore:
 
     def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None):
         """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
-        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, render_camera -- whose `prm` is its camera block; the next pass
+        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, bev_voxel_instances, render_camera -- whose `prm` is its camera block; the next pass
         of the family starts here): last_frame's default,
         the bound at which the window is cut (max_points; default: the live window's own) and -- side = (name,
         pca_*_workspace_bytes) -- the pass's scratch.  Returns (last_frame, max_points, call).
@@ -790,6 +790,54 @@ class DeviceStore:
         if mark_dyn:
             self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
         return {'hits': hits, 'cross': cross, 'flags': flags, 'stats': stats}
+
+    def bev_voxel_instances(self, prm, z_lo, z_step, nz, label_of, n_labels, min_points=1, connectivity=26, min_voxels=1,
+                            max_instances=4096, dyn='static', first_frame=0, last_frame=None, max_points=None):
+        """The object voxels of the live frames [first_frame, last_frame) clustered into instances (pca_bev_voxel_instances):
+        connected components of the voxels of bev_voxel_labels' grid that hold at least min_points kept points (same
+        geometry, same label_of / n_labels: the counts that are thresholded are bev_voxel_labels' counts).  dyn: 'static' --
+        points with dyn == 1 take no part; 'all' -- every point; 'dynamic' -- ONLY points with dyn == 1 (the movers after
+        bev_voxel_carve(mark_dyn=True), or of a NuScenes window).  connectivity 6 or 26 on (k, row, col), nothing wraps.  A
+        component survives with at least min_voxels voxels; the n survivors are numbered 0 .. n - 1 by their smallest place,
+        so the numbering does not depend on the order of the points.
+        Returns a dict of cuda tensors: 'inst' int32 [nz, px, px], the voxel's instance or -1; 'ids' int32, one per point of
+        the window in store order, the instance of a kept point's voxel or -1 (the window's exact length: one offset is read
+        back, the call synchronises); 'table' int32 [max_instances, 9] holding the u32 columns root place, voxels, kept
+        points, col_min, col_max, row_min, row_max, k_min, k_max (rows from n on are zero; host_logic.instance_boxes turns
+        them into metres); 'label_counts' int32 [max_instances, n_labels]; 'top_label' uint8 [max_instances], the most
+        frequent label of the instance, the smallest on a tie, 255 for an empty row; 'stats' int64 [6]: kept points,
+        foreground voxels, components, surviving components (n), kept points with an instance, voxels of the largest
+        surviving component.  'inst' and 'ids' are not capped by max_instances; the two tables are.
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        lib = self.ctx.lib
+        if dyn not in _lib.DYN_MODES:
+            raise ValueError("dyn must be 'static', 'all' or 'dynamic'")
+        label_table = np.ascontiguousarray(label_of, dtype=np.uint8)
+        if label_table.shape != (256, ):
+            raise ValueError('label_of must hold 256 entries')
+        args = [int(a) for a in (nz, n_labels, min_points, connectivity, min_voxels, max_instances)]
+        if any(not -(1 << 31) <= a < 1 << 31 for a in args):
+            raise ValueError('nz, n_labels, min_points, connectivity, min_voxels and max_instances must fit 32 bits')
+        nz, n_labels, min_points, connectivity, min_voxels, max_instances = args
+        last_frame, max_points, call = self._window_pass(
+            prm, first_frame, last_frame, max_points,
+            side=('inst', lambda m, px: lib.pca_bev_instances_workspace_bytes(m, px, nz, max_instances)))
+        px = int(prm.px)
+        rows = min(max(max_instances, 1), 65536)           # (a value outside 1..65536 is refused by the call)
+        inst = torch.empty((max(nz, 1), max(px, 1), max(px, 1)), dtype=torch.int32, device=self.device)
+        ids = torch.empty(max_points, dtype=torch.int32, device=self.device)
+        table = torch.empty((rows, _lib.BEV_INST_COLS), dtype=torch.int32, device=self.device)
+        label_counts = torch.empty((rows, min(max(n_labels, 1), 32)), dtype=torch.int32, device=self.device)
+        stats = torch.empty(6, dtype=torch.int64, device=self.device)
+        call(lib.pca_bev_voxel_instances, (float(z_lo), float(z_step), nz, label_table.ctypes.data, n_labels, _lib.DYN_MODES[dyn],
+                                           min_points, connectivity, min_voxels, max_instances),
+             (inst, ids, table, label_counts, stats))
+        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
+        n = min(int(lo_hi[1] - lo_hi[0]), max_points)
+        # the first maximum is the smallest label of a tie
+        top_label = torch.where(label_counts.sum(dim=1) > 0, label_counts.argmax(dim=1), 255).to(torch.uint8)
+        return {'inst': inst, 'ids': ids[:n], 'table': table, 'label_counts': label_counts, 'top_label': top_label, 'stats': stats}
 
     def render_camera(self, cam, first_frame=0, last_frame=None, classes=None, max_points=None):
         """The stored points of the live frames [first_frame, last_frame) rendered into a pinhole camera with a z-buffer

@@ -405,6 +405,25 @@ def pos2grid_inplace(mat, view, px):
     return mat
 
 
+def instance_boxes(table, n, view, px, z_lo, z_step):
+    """The voxel boxes of the first n rows of DeviceStore.bev_voxel_instances' table (columns 3..8: col_min, col_max,
+    row_min, row_max, k_min, k_max) in metres of the view frame: f64 [n, 6] as lo x, hi x, lo y, hi y, lo z, hi z.  A box
+    spans whole voxels: cell i covers [(i - px / 2) view / px, (i + 1 - px / 2) view / px) and bin k covers
+    [z_lo + k z_step, z_lo + (k + 1) z_step).  Columns are i; rows are image rows, row = px - 1 - j, so the smallest y
+    belongs to the LARGEST row.  (A metric box tighter than the voxels is not computed anywhere.)"""
+    t = np.asarray(table).reshape(-1, 9)[:int(n)].astype(np.int64) & 0xffffffff    # (int32 that holds u32)
+    cell = float(view) / px
+    half = 0.5 * px
+    out = np.empty((t.shape[0], 6), dtype=np.float64)
+    out[:, 0] = (t[:, 3] - half) * cell
+    out[:, 1] = (t[:, 4] + 1 - half) * cell
+    out[:, 2] = (px - 1 - t[:, 6] - half) * cell
+    out[:, 3] = (px - 1 - t[:, 5] + 1 - half) * cell
+    out[:, 4] = z_lo + t[:, 7] * float(z_step)
+    out[:, 5] = z_lo + (t[:, 8] + 1) * float(z_step)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 #  trajectories
 # ----------------------------------------------------------------------------------------------

@@ -406,6 +406,26 @@ class SemanticPointCloudAccumulator:
         return gen.voxel_carve_device(pc, origins, rot_mat, 0., 0., view, z_range, nz, classes=classes, end_margin=end_margin,
                                       min_cross=min_cross, ratio=ratio, include_dyn=False, mark_dyn=mark_dyn)
 
+    def voxel_instances(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, min_points=1, connectivity=26,
+                        min_voxels=1, max_instances=4096, dyn='static'):
+        """Extension (no reference counterpart): which points form one object.  The points of `classes` in `part` ('present' |
+        'future' | 'full') of the sample generate_bev(present_idx, 1, True) would make, clustered on the grid of voxel_labels
+        in that sample's un-augmented frame: a voxel with at least min_points such points is foreground, foreground voxels
+        that touch (connectivity 6: by a face; 26: by a face, an edge or a corner) form a component, a component of at least
+        min_voxels voxels is an instance, and the instances are numbered by their smallest voxel index -- the same points in
+        any order give the same numbers.  classes: a list of class lists, list i becomes label i; None: the generator's
+        dynamic classes (car, truck, bus, motorcycle), one label each.  dyn: 'static' -- points with dyn == 1 take no part
+        (the parked things); 'all'; 'dynamic' -- only points with dyn == 1 (the movers after carve_dynamic(mark_dyn=True), or
+        of a NuScenes window).
+        Returns DeviceStore.bev_voxel_instances' dict of cuda tensors: 'inst' [nz, px, px], 'ids' (one per point of the
+        part), 'table' (voxel boxes and counts: pca_amd.host_logic.instance_boxes gives metres), 'label_counts', 'top_label',
+        'stats'.  Nothing is written: the store, the owed re-transforms and every later sample stay as they are.
+        integrate() never calls this on its own."""
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        return self.sem_bev_generator.voxel_instances_device(pc, rot_mat, 0., 0., view, z_range, nz, classes=classes,
+                                                             min_points=min_points, connectivity=connectivity,
+                                                             min_voxels=min_voxels, max_instances=max_instances, dyn=dyn)
+
     def _render_defaults(self):
         """(P, (W, H)) of render_camera where the dataset has one camera the stored coordinates belong to; (None, None) here."""
         return None, None
