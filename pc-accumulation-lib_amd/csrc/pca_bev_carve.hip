@@ -4,10 +4,10 @@
 // drop rules, the traversal and its tie order are those of bev_voxel_rays, from the one copy in pca_bev_ray_setup.h.
 //
 //   bev_carve_ends   one thread per stored point of the window, 256 threads, a grid-stride loop over chunks of 256 points with
-//                    the chunk / slot walk of bev_voxel_rays.  The end voxel of the point's ray: vox[p] = its place in the
+//                    the window and the chunk / slot walk of pca_point_pass.h.  The end voxel of the point's ray: vox[p] = its place in the
 //                    output, or -1 (the point takes no part, its ray is dropped, or it ends outside the grid); a no-return
 //                    u32 atomic add on hits; a byte store of 1 into cand for a point of a class in `only` (every writer writes
-//                    the same value).  Counters 0..3 per lane, per wave, LDS, one global add per counter and workgroup.
+//                    the same value).  Counters 0..3 per lane, then point_count (pca_point_pass.h).
 //   bev_carve_rays   the traversal, stopped end_margin steps before the end voxel.  Per step inside the grid a byte load of
 //                    cand (u8 [nz][px][px], 2 MiB at 256^2 x 32: it stays in L2) and, only where that reads 1, a no-return
 //                    u32 atomic add on cross: global atomics execute at the memory side, and scattered ones run far below
@@ -20,9 +20,7 @@
 // surface from carving itself (the neighbouring beams of one surface cross its own voxels just before they end); nothing calls
 // this from integrate().  All sums are integer sums: the result does not depend on the order.  The store is never written.
 #include "pca_bev_ray_setup.h"
-
-#define CARVE_THREADS 256
-#define CARVE_MAX_G 2048          // workgroups at most of the first two kernels
+#include "pca_point_pass.h"
 
 struct alignas(16) CarveArgs {
     pca_store st;
@@ -47,32 +45,11 @@ struct alignas(16) CarveArgs {
     uint32_t *status;             // context status word (PCA_STATUS_* bits)
 };
 
-// the window's points [lo, hi): cut at max_points and at the capacity (nothing is stored behind it, whatever frame_off counts)
-__device__ __forceinline__ int64_t carve_window(const CarveArgs &a, int64_t &lo, bool &cut)
-{
-    lo = pca_sload(a.frame_off + a.slot_begin);
-    const int64_t hi0 = pca_sload(a.frame_off + a.slot_end);
-    cut = hi0 - lo > a.max_points;
-    const int64_t hi = cut ? lo + a.max_points : hi0;
-    return hi > a.st.capacity ? a.st.capacity : hi;
-}
-// the slot of a chunk's first point: the last one with frame_off[slot] <= c_lo (scalar: the chunk is workgroup-uniform)
-__device__ __forceinline__ int carve_chunk_slot(const CarveArgs &a, int64_t c_lo)
-{
-    int s_lo = a.slot_begin, s_hi = a.slot_end;
-    while (s_hi - s_lo > 1) {
-        const int mid = (s_lo + s_hi) >> 1;
-        if (pca_sload(a.frame_off + mid) <= c_lo) s_lo = mid; else s_hi = mid;
-    }
-    return s_lo;
-}
 // The ray of point p (which takes part): start and end in grid coordinates.  Returns whether all six are usable.
 __device__ __forceinline__ bool carve_ray(const CarveArgs &a, const RayGrid &q, const PendHi &pend_hi, int64_t p, int s_lo,
                                           double &s0, double &s1, double &s2, double &e0, double &e1, double &e2)
 {
-    // the lane's own slot (p < hi <= frame_off[slot_end]: the walk ends below slot_end; empty frames are stepped over)
-    int slot = s_lo;
-    while (slot + 1 < a.slot_end && pca_ldg(a.frame_off + slot + 1) <= p) ++slot;
+    const int slot = point_lane_slot(a, s_lo, p);
     double X = pca_ldg(a.st.x + p), Y = pca_ldg(a.st.y + p), Z = pca_ldg(a.st.z + p);
     apply_owed(a.owed, pend_hi, p, X, Y, Z);
     const double *o = a.origins + (int64_t)(slot - a.slot_begin) * 3;
@@ -81,23 +58,18 @@ __device__ __forceinline__ bool carve_ray(const CarveArgs &a, const RayGrid &q, 
     return ray_coord_ok(s0) && ray_coord_ok(s1) && ray_coord_ok(s2) && ray_coord_ok(e0) && ray_coord_ok(e1) && ray_coord_ok(e2);
 }
 
-__global__ __launch_bounds__(CARVE_THREADS) void bev_carve_ends(const CarveArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void bev_carve_ends(const CarveArgs a)
 {
-    __shared__ unsigned long long s_stat[4];
     const int tid = (int)threadIdx.x;
-    if (tid < 4) s_stat[tid] = 0;
-    __syncthreads();
-    int64_t lo;
-    bool cut;
-    const int64_t hi = carve_window(a, lo, cut);
-    if (blockIdx.x == 0 && tid == 0 && cut) pca_raise(a.status, PCA_STATUS_STORE_OVERFLOW);
+    const PointWindow w = point_window<true>(a);
+    const int64_t lo = w.lo, hi = w.hi;
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
     const RayGrid q = ray_grid(a.prm, a.z_lo, a.z_step);
     const int px = a.prm.px, nz = a.nz;
     uint32_t n_part = 0, n_cast = 0, n_not_finite = 0, n_too_long = 0;
 
-    for (int64_t c_lo = lo + (int64_t)blockIdx.x * CARVE_THREADS; c_lo < hi; c_lo += (int64_t)a.G * CARVE_THREADS) {
-        const int s_lo = carve_chunk_slot(a, c_lo);
+    for (int64_t c_lo = lo + (int64_t)blockIdx.x * POINT_THREADS; c_lo < hi; c_lo += (int64_t)a.G * POINT_THREADS) {
+        const int s_lo = point_chunk_slot(a, c_lo);
         const int64_t p = c_lo + tid;
         if (p >= hi) continue;
         int32_t place = -1;
@@ -122,33 +94,21 @@ __global__ __launch_bounds__(CARVE_THREADS) void bev_carve_ends(const CarveArgs 
         }
         a.vox[p - lo] = place;
     }
-
-    // the counters: wave, LDS, one global add per counter
-    const uint32_t w_part = wave_reduce_add(n_part), w_cast = wave_reduce_add(n_cast);
-    const uint32_t w_not_finite = wave_reduce_add(n_not_finite), w_too_long = wave_reduce_add(n_too_long);
-    if ((tid & 63) == 0) {
-        atomicAdd(&s_stat[0], (unsigned long long)w_part);
-        atomicAdd(&s_stat[1], (unsigned long long)w_cast);
-        atomicAdd(&s_stat[2], (unsigned long long)w_not_finite);
-        atomicAdd(&s_stat[3], (unsigned long long)w_too_long);
-    }
-    __syncthreads();
-    if (tid < 4 && a.stats && s_stat[tid]) atomicAdd(a.stats + tid, s_stat[tid]);
+    point_count(a.stats, n_part, n_cast, n_not_finite, n_too_long);
 }
 
-__global__ __launch_bounds__(CARVE_THREADS) void bev_carve_rays(const CarveArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void bev_carve_rays(const CarveArgs a)
 {
     const int tid = (int)threadIdx.x;
-    int64_t lo;
-    bool cut;
-    const int64_t hi = carve_window(a, lo, cut);
+    const PointWindow w = point_window<false>(a);
+    const int64_t lo = w.lo, hi = w.hi;
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
     const RayGrid q = ray_grid(a.prm, a.z_lo, a.z_step);
     const int px = a.prm.px, nz = a.nz;
     auto *cand = reinterpret_cast<const __attribute__((address_space(1))) uint8_t *>(reinterpret_cast<uintptr_t>(a.cand));
 
-    for (int64_t c_lo = lo + (int64_t)blockIdx.x * CARVE_THREADS; c_lo < hi; c_lo += (int64_t)a.G * CARVE_THREADS) {
-        const int s_lo = carve_chunk_slot(a, c_lo);
+    for (int64_t c_lo = lo + (int64_t)blockIdx.x * POINT_THREADS; c_lo < hi; c_lo += (int64_t)a.G * POINT_THREADS) {
+        const int s_lo = point_chunk_slot(a, c_lo);
         const int64_t p = c_lo + tid;
         if (p >= hi) continue;
         if (!a.include_dyn && pca_ldg(a.st.dyn + p) == 1) continue;
@@ -182,16 +142,11 @@ __global__ __launch_bounds__(CARVE_THREADS) void bev_carve_rays(const CarveArgs 
     }
 }
 
-__global__ __launch_bounds__(CARVE_THREADS) void bev_carve_flags(const CarveArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void bev_carve_flags(const CarveArgs a)
 {
-    __shared__ unsigned long long s_stat[2];
-    const int tid = (int)threadIdx.x;
-    if (tid < 2) s_stat[tid] = 0;
-    __syncthreads();
-    int64_t lo;
-    bool cut;
-    const int64_t hi = carve_window(a, lo, cut);
-    const int64_t p = lo + (int64_t)blockIdx.x * CARVE_THREADS + tid;
+    const PointWindow w = point_window<false>(a);
+    const int64_t lo = w.lo, hi = w.hi;
+    const int64_t p = lo + (int64_t)blockIdx.x * POINT_THREADS + threadIdx.x;
     uint32_t n_cand = 0, n_flagged = 0;
     if (p < hi) {
         uint8_t flag = 255;
@@ -204,13 +159,7 @@ __global__ __launch_bounds__(CARVE_THREADS) void bev_carve_flags(const CarveArgs
         }
         if (a.flags) a.flags[p - lo] = flag;
     }
-    const uint32_t w_cand = wave_reduce_add(n_cand), w_flagged = wave_reduce_add(n_flagged);
-    if ((tid & 63) == 0) {
-        atomicAdd(&s_stat[0], (unsigned long long)w_cand);
-        atomicAdd(&s_stat[1], (unsigned long long)w_flagged);
-    }
-    __syncthreads();
-    if (tid < 2 && a.stats && s_stat[tid]) atomicAdd(a.stats + 4 + tid, s_stat[tid]);
+    point_count(a.stats ? a.stats + 4 : nullptr, n_cand, n_flagged);
 }
 
 static const WindowPass CARVE_PASS = {"bev voxel carve", true, false};
@@ -262,10 +211,7 @@ int pca_bev_voxel_carve(pca_ctx *ctx, const pca_store *store, const int64_t *fra
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     A.z_lo = z_lo; A.z_step = z_step;
     A.nz = nz; A.include_dyn = include_dyn;
-    const int64_t chunks = (max_points + CARVE_THREADS - 1) / CARVE_THREADS;
-    // PCA_BEV_CARVE_G: a cap on the workgroups, read on every call (tests set it to send a workgroup round its loop again)
-    const int64_t max_g = pca_env_int("PCA_BEV_CARVE_G", CARVE_MAX_G, 1, CARVE_MAX_G);
-    A.G = (int)(chunks > max_g ? max_g : chunks);
+    A.G = point_pass_G(max_points, "PCA_BEV_CARVE_G");
     A.end_margin = end_margin; A.min_cross = min_cross; A.ratio = ratio;
     for (int i = 0; i < 4; ++i) A.only.w[i] = only->mask[i];
     A.origins = origins;
@@ -285,10 +231,10 @@ int pca_bev_voxel_carve(pca_ctx *ctx, const pca_store *store, const int64_t *fra
     const CarveArgs &args = A;
     if (slot_end > slot_begin)                              // (a window without a slot: no launch over zero points)
     {
-        PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_ENDS, bev_carve_ends, dim3(args.G), dim3(CARVE_THREADS), s, args);
-        PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_RAYS, bev_carve_rays, dim3(args.G), dim3(CARVE_THREADS), s, args);
+        PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_ENDS, bev_carve_ends, dim3(args.G), dim3(POINT_THREADS), s, args);
+        PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_RAYS, bev_carve_rays, dim3(args.G), dim3(POINT_THREADS), s, args);
         if (flags || stats)
-            PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_FLAGS, bev_carve_flags, dim3((unsigned)chunks), dim3(CARVE_THREADS), s, args);
+            PCA_LAUNCH(ctx, PCA_K_BEV_CARVE_FLAGS, bev_carve_flags, dim3((unsigned)point_chunks(max_points)), dim3(POINT_THREADS), s, args);
     }
     PCA_CHECK(ctx, hipGetLastError());
     return 0;

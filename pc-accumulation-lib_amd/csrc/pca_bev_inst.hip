@@ -27,7 +27,8 @@
 //                      that id (else -1) and row id of the table its root, size and the identities of its extremes.
 //   bev_inst_write     inst[v] = id of parent[v]; the six extremes by atomicMin / atomicMax on the table, aggregated as below.
 //   bev_inst_points    one thread per window point: the key, ids[p] = inst[voxel] (or -1), and the adds on table[id].points and
-//                      label_counts[id][label], aggregated as below.
+//                      label_counts[id][label], aggregated as below.  Its window is pca_point_pass.h's, as are the counters
+//                      of init, sums and points (point_count).
 // Aggregation (compress, write, points): on the headline window, whose classes are uniform, ONE component takes 390 000 voxels
 // and 450 000 points, and one global atomic per voxel or point on its row serialises (4.4 + 2.1 + 1.7 ms of a call of 8.7 ms
 // without it).  So the lanes of a wave that share a key are counted by ballot (or reduced with the wave's min / max) and their
@@ -38,9 +39,9 @@
 // Scope: the boxes are voxel boxes (a metric box tighter than the voxels is not computed); the tile-local LDS stage for the
 // merge is not built (profiles/bev_voxel_instances.txt has the plain form's time).  The store is never written.
 #include "pca_bev_voxel.h"
+#include "pca_point_pass.h"
 
-#define INST_THREADS 256
-#define INST_MAX_G 2048           // workgroups at most of every kernel but bev_inst_offsets
+#define INST_THREADS POINT_THREADS // (with POINT_MAX_G the one pair of pca_point_pass.h, for every kernel but bev_inst_offsets)
 #define INST_TILE 4096            // voxels per scan tile: 16 per thread
 #define INST_PER (INST_TILE / INST_THREADS)
 
@@ -84,19 +85,6 @@ __device__ __forceinline__ void inst_unite(int32_t *parent, int32_t a, int32_t b
         a = old;                                            // somebody linked a first: unite what it wrote with b
     }
 }
-// one counter of a workgroup: wave, LDS, one global add (all threads call it)
-__device__ __forceinline__ void inst_count(unsigned long long *dst, uint32_t n, uint32_t *s_sum)
-{
-    const int tid = (int)threadIdx.x;
-    __syncthreads();
-    if (tid == 0) *s_sum = 0;
-    __syncthreads();
-    const uint32_t w = wave_reduce_add(n);
-    if ((tid & 63) == 0 && w) atomicAdd(s_sum, w);
-    __syncthreads();
-    if (tid == 0 && dst && *s_sum) atomicAdd(dst, (unsigned long long)*s_sum);
-}
-
 // Every lane calls it with its key (0xffffffff: none).  f(key, lanes, leader) runs once per DISTINCT key of the wave, on all
 // lanes (it may reduce over the wave): `lanes` = the ballot of the lanes that hold the key, `leader` = this lane is their first.
 template <typename F>
@@ -133,7 +121,6 @@ __device__ __forceinline__ int inst_slots_claim(InstSlots &s, uint32_t key)
 
 __global__ __launch_bounds__(INST_THREADS) void bev_inst_init(const InstArgs a)
 {
-    __shared__ uint32_t s_sum;
     uint32_t n = 0;
     for (int64_t v = (int64_t)blockIdx.x * INST_THREADS + threadIdx.x; v < a.cells; v += (int64_t)a.G * INST_THREADS) {
         const bool fg = pca_ldg(a.counts + v) >= a.min_points;
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(INST_THREADS) void bev_inst_init(const InstArgs a)
         a.size[v] = 0;
         n += fg;
     }
-    inst_count(a.stats ? a.stats + 1 : nullptr, n, &s_sum);
+    point_count(a.stats ? a.stats + 1 : nullptr, n);
 }
 
 template <int PHASE>
@@ -201,7 +188,7 @@ __global__ __launch_bounds__(INST_THREADS) void bev_inst_compress(const InstArgs
 
 __global__ __launch_bounds__(INST_THREADS) void bev_inst_sums(const InstArgs a)
 {
-    __shared__ uint32_t s_sum, s_w[INST_THREADS / 64];
+    __shared__ uint32_t s_w[INST_THREADS / 64];
     const int tid = (int)threadIdx.x;
     uint32_t n_roots = 0, largest = 0;
     for (int tile = (int)blockIdx.x; tile < a.tiles; tile += a.G) {
@@ -219,7 +206,7 @@ __global__ __launch_bounds__(INST_THREADS) void bev_inst_sums(const InstArgs a)
         if (tid == 0) a.partial[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
         __syncthreads();
     }
-    inst_count(a.stats ? a.stats + 2 : nullptr, n_roots, &s_sum);
+    point_count(a.stats ? a.stats + 2 : nullptr, n_roots);
     const uint32_t w_largest = wave_reduce_max(largest);
     if ((tid & 63) == 0 && a.stats && w_largest) atomicMax(a.stats + 5, (unsigned long long)w_largest);
 }
@@ -318,16 +305,13 @@ __global__ __launch_bounds__(INST_THREADS) void bev_inst_write(const InstArgs a)
 __global__ __launch_bounds__(INST_THREADS) void bev_inst_points(const InstArgs a)
 {
     __shared__ uint8_t s_label[256];
-    __shared__ uint32_t s_sum;
     __shared__ InstSlots s_slots;
     const int tid = (int)threadIdx.x;
     s_label[tid] = a.v.label_of[tid];
     inst_slots_init(s_slots, false);
     const SideArgs &s = a.v.s;
-    // the window [lo, hi): cut at max_points, as the voxel pass cuts it (and at the capacity: nothing is stored behind it)
-    const int64_t lo = pca_sload(s.frame_off + s.slot_begin), hi0 = pca_sload(s.frame_off + s.slot_end);
-    int64_t hi = hi0 - lo > s.max_points ? lo + s.max_points : hi0;
-    hi = hi > s.st.capacity ? s.st.capacity : hi;
+    const PointWindow w = point_window<false>(s);          // (cut at max_points as the voxel pass cuts it, which raises the bit)
+    const int64_t lo = w.lo, hi = w.hi;
     const PendHi pend_hi = owed_bounds(s.owed, s.frame_off, s.slot_begin, lo);
     const ViewConst vc = view_const(s.prm, s.tx, 0, 0);
     const int px = s.prm.px, nl = a.v.n_labels;
@@ -365,8 +349,8 @@ __global__ __launch_bounds__(INST_THREADS) void bev_inst_points(const InstArgs a
         if (a.table) atomicAdd(a.table + (size_t)id * PCA_BEV_INST_COLS + 2, n);
         if (a.label_counts) atomicAdd(a.label_counts + (size_t)id * nl + (kk & 31u), n);
     }
-    inst_count(a.stats ? a.stats + 0 : nullptr, n_kept, &s_sum);
-    inst_count(a.stats ? a.stats + 4 : nullptr, n_with, &s_sum);
+    point_count(a.stats, n_kept);
+    point_count(a.stats ? a.stats + 4 : nullptr, n_with);
 }
 
 static const WindowPass INST_PASS = {"bev voxel instances", true, false};
@@ -426,11 +410,8 @@ int pca_bev_voxel_instances(pca_ctx *ctx, const pca_store *store, const int64_t 
     if (max_instances < 1 || max_instances > 65536) { ctx->err = w + ": max_instances must be in 1..65536"; return -1; }
     A.cells = (int64_t)nz * prm->px * prm->px;
     A.conn = connectivity;
-    // PCA_BEV_INST_G: a cap on the workgroups, read on every call (tests set it to send a workgroup round its loop again)
-    const int64_t max_g = pca_env_int("PCA_BEV_INST_G", INST_MAX_G, 1, INST_MAX_G);
-    const int64_t blocks = (A.cells + INST_THREADS - 1) / INST_THREADS, chunks = (max_points + INST_THREADS - 1) / INST_THREADS;
-    A.G = (int)(blocks > max_g ? max_g : blocks);
-    A.Gp = (int)(chunks > max_g ? max_g : chunks);
+    A.G = point_pass_G(A.cells, "PCA_BEV_INST_G");          // (one voxel per thread and round: the grid's chunks, the same cap)
+    A.Gp = point_pass_G(max_points, "PCA_BEV_INST_G");
     A.tiles = l.tiles;
     A.min_points = (uint32_t)min_points; A.min_voxels = (uint32_t)min_voxels; A.max_instances = (uint32_t)max_instances;
     A.counts = reinterpret_cast<uint32_t *>(base + l.counts);

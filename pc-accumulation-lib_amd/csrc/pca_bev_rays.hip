@@ -3,8 +3,8 @@
 // (a beam passed) and unseen (none did) -- the "invalid" mask of SemanticKITTI-SSC / SSCBench-KITTI-360 ground truth.
 //
 //   bev_voxel_rays   one thread per stored point of the window, 256 threads, a grid-stride loop over chunks of 256 points.
-//                    The slot of a chunk's first point by a binary search over frame_off in scalar loads (the chunk is
-//                    workgroup-uniform), a lane's own slot by walking on from there; the slot's sensor position and the
+//                    The window, the slot of a chunk's first point and a lane's own slot are those of pca_point_pass.h (a
+//                    binary search over frame_off in scalar loads, then a walk per lane); the slot's sensor position and the
 //                    point (owed re-transforms applied: pca_bev_view.h) into grid coordinates -- f64, nothing fused, the
 //                    IEEE divisions, the UNFUSED product sum (unlike the view test: a numpy model restates it bit for bit);
 //                    Amanatides-Woo driven by the integer step counts, so that it always ends in the end voxel, which is
@@ -16,12 +16,12 @@
 //                    profiles/bev_voxel_rays.txt).  A ray leaves its loop early only by integer tests that cannot change
 //                    the marked set.  The four counters: per lane, per wave, LDS, one global add per counter and workgroup.
 // The store is never written.  PCA_BEV_RAYS_MAX_STEPS bounds every ray, hence every launch.  The grid coordinates and the
-// ray's set-up (voxels, step counts, tMax, tDelta) come from pca_bev_ray_setup.h, shared with pca_bev_carve.hip; the step
-// loop below stays written out here, as it was tuned.
+// ray's set-up (voxels, step counts, tMax, tDelta) come from pca_bev_ray_setup.h, shared with pca_bev_carve.hip.  The step
+// loop and the counters' epilogue stay written out here, as they were tuned: the kernel sits at 100 scalar registers, and with
+// ray_box_misses / ray_gone / ray_advance or with point_count (pca_point_pass.h) in their place the step loop gains 9 to 17
+// v_readlane of spilled scalars: 1.625 and 1.627 ms against 1.554-1.559 (profiles/point_pass_refactor_ab.txt).
 #include "pca_bev_ray_setup.h"
-
-#define RAY_THREADS 256
-#define RAY_MAX_G 2048            // workgroups at most (eight per CU; the registers let six of them be resident)
+#include "pca_point_pass.h"
 
 struct alignas(16) RayArgs {
     pca_store st;
@@ -40,17 +40,14 @@ struct alignas(16) RayArgs {
 };
 
 template <bool ALWAYS_STORE>
-__global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void bev_voxel_rays(const RayArgs a)
 {
     __shared__ unsigned long long s_stat[4];
     const int tid = (int)threadIdx.x;
     if (tid < 4) s_stat[tid] = 0;
     __syncthreads();
-    const int64_t lo = pca_sload(a.frame_off + a.slot_begin);
-    const int64_t hi0 = pca_sload(a.frame_off + a.slot_end);
-    int64_t hi = (hi0 - lo > a.max_points) ? lo + a.max_points : hi0;
-    if (hi > a.st.capacity) hi = a.st.capacity;            // (nothing is stored behind the capacity, whatever frame_off counts)
-    if (blockIdx.x == 0 && tid == 0 && hi0 - lo > a.max_points) pca_raise(a.status, PCA_STATUS_STORE_OVERFLOW);
+    const PointWindow w = point_window<true>(a);
+    const int64_t lo = w.lo, hi = w.hi;
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
     const RayGrid q = ray_grid(a.prm, a.z_lo, a.z_step);
     const int px = a.prm.px, nz = a.nz;
@@ -58,18 +55,11 @@ __global__ __launch_bounds__(RAY_THREADS) void bev_voxel_rays(const RayArgs a)
     const double INF = __builtin_huge_val();
     uint32_t n_considered = 0, n_cast = 0, n_not_finite = 0, n_too_long = 0;
 
-    for (int64_t c_lo = lo + (int64_t)blockIdx.x * RAY_THREADS; c_lo < hi; c_lo += (int64_t)a.G * RAY_THREADS) {
-        // the slot of the chunk's first point: the last one with frame_off[slot] <= c_lo (scalar: the chunk is uniform)
-        int s_lo = a.slot_begin, s_hi = a.slot_end;
-        while (s_hi - s_lo > 1) {
-            const int mid = (s_lo + s_hi) >> 1;
-            if (pca_sload(a.frame_off + mid) <= c_lo) s_lo = mid; else s_hi = mid;
-        }
+    for (int64_t c_lo = lo + (int64_t)blockIdx.x * POINT_THREADS; c_lo < hi; c_lo += (int64_t)a.G * POINT_THREADS) {
+        const int s_lo = point_chunk_slot(a, c_lo);
         const int64_t p = c_lo + tid;
         if (p >= hi) continue;
-        // the lane's own slot (p < hi <= frame_off[slot_end]: the walk ends below slot_end; empty frames are stepped over)
-        int slot = s_lo;
-        while (slot + 1 < a.slot_end && pca_ldg(a.frame_off + slot + 1) <= p) ++slot;
+        const int slot = point_lane_slot(a, s_lo, p);
         if (!a.include_dyn && pca_ldg(a.st.dyn + p) == 1) continue;
         ++n_considered;
         double X = pca_ldg(a.st.x + p), Y = pca_ldg(a.st.y + p), Z = pca_ldg(a.st.z + p);
@@ -163,10 +153,7 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
     if (voxel_grid_check(ctx, RAY_PASS.what, z_lo, z_step, nz)) return -1;
     A.z_lo = z_lo; A.z_step = z_step;
     A.nz = nz; A.include_dyn = include_dyn;
-    const int64_t chunks = (max_points + RAY_THREADS - 1) / RAY_THREADS;
-    // PCA_BEV_RAYS_G: a cap on the workgroups, read on every call (tests set it to send a workgroup round its loop again)
-    const int64_t max_g = pca_env_int("PCA_BEV_RAYS_G", RAY_MAX_G, 1, RAY_MAX_G);
-    A.G = (int)(chunks > max_g ? max_g : chunks);
+    A.G = point_pass_G(max_points, "PCA_BEV_RAYS_G");
     A.origins = origins;
     A.seen = seen;
     A.stats = reinterpret_cast<unsigned long long *>(stats);
@@ -178,9 +165,9 @@ int pca_bev_voxel_rays(pca_ctx *ctx, const pca_store *store, const int64_t *fram
     if (slot_end > slot_begin)                              // (a window without a slot: no launch over zero points)
     {
         if (pca_env_int("PCA_BEV_RAYS_STORE", 0, 0, 1))     // A/B: 1 = every mark stores, without the load in front (same result)
-            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<true>, dim3(args.G), dim3(RAY_THREADS), s, args);
+            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<true>, dim3(args.G), dim3(POINT_THREADS), s, args);
         else
-            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<false>, dim3(args.G), dim3(RAY_THREADS), s, args);
+            PCA_LAUNCH(ctx, PCA_K_BEV_VOXEL_RAYS, bev_voxel_rays<false>, dim3(args.G), dim3(POINT_THREADS), s, args);
     }
     PCA_CHECK(ctx, hipGetLastError());
     return 0;

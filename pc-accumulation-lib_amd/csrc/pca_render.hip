@@ -10,15 +10,12 @@
 //                    rounded to f32 and, among equal depths, the smallest window index -- whatever the order of arrival.
 //                    A pixel's key is read with a plain load first and the atomic issued only where the key is below it: keys
 //                    only ever fall, so a stale value costs a redundant atomic and never loses a minimum (ALWAYS_ATOMIC:
-//                    the A/B form without the load, same result).  The two counters: per lane, per wave, LDS, one global
-//                    add per counter and workgroup.
+//                    the A/B form without the load, same result).  The two counters: per lane, then point_count.
 //   render_resolve   one thread per pixel: the key taken apart into depth and index, colour and class gathered from the
 //                    winner's rgbs word; the covered pixels counted the same way.
-// The store is never written.
-#include "pca_bev_view.h"
+// The window, its cuts and the counters' way to memory are those of pca_point_pass.h.  The store is never written.
+#include "pca_point_pass.h"
 
-#define RENDER_THREADS 256
-#define RENDER_MAX_G 2048         // workgroups at most (eight per CU)
 #define RENDER_MAX_PIXELS (1 << 24)
 #define RENDER_MAX_RADIUS 3
 #define RENDER_EMPTY 0xffffffffffffffffull
@@ -64,33 +61,18 @@ __device__ __forceinline__ bool render_inside(const RenderProj &q, int W, int H,
     return (q.uf >= 0.0) && (q.uf < (double)W) && (q.vf >= 0.0) && (q.vf < (double)H) && (q.d > d_lo) && (q.d < d_hi);
 }
 
-// the window's points [lo, hi): cut at max_points and at the capacity (nothing is stored behind it, whatever frame_off counts)
-__device__ __forceinline__ int64_t render_window(const RenderArgs &a, int64_t &lo, bool &cut)
-{
-    lo = pca_sload(a.frame_off + a.slot_begin);
-    const int64_t hi0 = pca_sload(a.frame_off + a.slot_end);
-    cut = hi0 - lo > a.max_points;
-    const int64_t hi = cut ? lo + a.max_points : hi0;
-    return hi > a.st.capacity ? a.st.capacity : hi;
-}
-
 template <bool ALWAYS_ATOMIC>
-__global__ __launch_bounds__(RENDER_THREADS) void render_zbuffer(const RenderArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void render_zbuffer(const RenderArgs a)
 {
-    __shared__ unsigned long long s_stat[2];
     const int tid = (int)threadIdx.x;
-    if (tid < 2) s_stat[tid] = 0;
-    __syncthreads();
-    int64_t lo;
-    bool cut;
-    const int64_t hi = render_window(a, lo, cut);
-    if (blockIdx.x == 0 && tid == 0 && cut) pca_raise(a.status, PCA_STATUS_STORE_OVERFLOW);
+    const PointWindow w = point_window<true>(a);
+    const int64_t lo = w.lo, hi = w.hi;
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, lo);
     const int W = a.W, H = a.H, rad = a.radius;
     auto *keys = reinterpret_cast<__attribute__((address_space(1))) unsigned long long *>(reinterpret_cast<uintptr_t>(a.keys));
     uint32_t n_considered = 0, n_kept = 0;
 
-    for (int64_t p = lo + (int64_t)blockIdx.x * RENDER_THREADS + tid; p < hi; p += (int64_t)a.G * RENDER_THREADS) {
+    for (int64_t p = lo + (int64_t)blockIdx.x * POINT_THREADS + tid; p < hi; p += (int64_t)a.G * POINT_THREADS) {
         if (!a.include_dyn && pca_ldg(a.st.dyn + p) == 1) continue;
         if (a.use_only && !in_mask(a.only, pca_ldg(a.st.rgbs + p) >> 24)) continue;
         ++n_considered;
@@ -111,27 +93,13 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_zbuffer(const RenderArg
                     __hip_atomic_fetch_min(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
     }
-
-    // the counters: wave, LDS, one global add per counter
-    const uint32_t w_considered = wave_reduce_add(n_considered), w_kept = wave_reduce_add(n_kept);
-    if ((tid & 63) == 0) {
-        atomicAdd(&s_stat[0], (unsigned long long)w_considered);
-        atomicAdd(&s_stat[1], (unsigned long long)w_kept);
-    }
-    __syncthreads();
-    if (tid < 2 && s_stat[tid]) atomicAdd(a.stats + tid, s_stat[tid]);
+    point_count(a.stats, n_considered, n_kept);
 }
 
-__global__ __launch_bounds__(RENDER_THREADS) void render_resolve(const RenderArgs a)
+__global__ __launch_bounds__(POINT_THREADS) void render_resolve(const RenderArgs a)
 {
-    __shared__ unsigned long long s_covered;
-    const int tid = (int)threadIdx.x;
-    if (tid == 0) s_covered = 0;
-    __syncthreads();
-    int64_t lo;
-    bool cut;
-    render_window(a, lo, cut);
-    const int64_t pix = (int64_t)blockIdx.x * RENDER_THREADS + tid;
+    const int64_t lo = point_window<false>(a).lo;
+    const int64_t pix = (int64_t)blockIdx.x * POINT_THREADS + threadIdx.x;
     uint32_t covered = 0;
     if (pix < (int64_t)a.W * a.H) {
         const unsigned long long key = pca_ldg(a.keys + pix);
@@ -151,10 +119,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_resolve(const RenderArg
         a.rgb[pix * 3 + 2] = (uint8_t)(c >> 16);
         a.sem[pix] = (uint8_t)(c >> 24);
     }
-    const uint32_t w_covered = wave_reduce_add(covered);
-    if ((tid & 63) == 0) atomicAdd(&s_covered, (unsigned long long)w_covered);
-    __syncthreads();
-    if (tid == 0 && s_covered) atomicAdd(a.stats + 2, s_covered);
+    point_count(a.stats + 2, covered);
 }
 
 static const WindowPass RENDER_PASS = {"render camera", true, false};
@@ -192,10 +157,7 @@ int pca_render_camera(pca_ctx *ctx, const pca_store *store, const int64_t *frame
     A.min_depth = cam->min_depth; A.max_depth = cam->max_depth;
     for (int i = 0; i < 4; ++i) A.only.w[i] = only ? only->mask[i] : 0;
     A.use_only = only ? 1 : 0;
-    const int64_t chunks = (max_points + RENDER_THREADS - 1) / RENDER_THREADS;
-    // PCA_RENDER_G: a cap on the workgroups, read on every call (tests set it to send a workgroup round its loop again)
-    const int64_t max_g = pca_env_int("PCA_RENDER_G", RENDER_MAX_G, 1, RENDER_MAX_G);
-    A.G = (int)(chunks > max_g ? max_g : chunks);
+    A.G = point_pass_G(max_points, "PCA_RENDER_G");
     A.keys = reinterpret_cast<unsigned long long *>(keys);
     A.depth = depth; A.index = index; A.rgb = rgb; A.sem = sem;
     A.stats = reinterpret_cast<unsigned long long *>(stats);
@@ -208,12 +170,12 @@ int pca_render_camera(pca_ctx *ctx, const pca_store *store, const int64_t *frame
     if (slot_end > slot_begin)                              // (a window without a slot: no launch over zero points)
     {
         if (pca_env_int("PCA_RENDER_ALWAYS_ATOMIC", 0, 0, 1))   // A/B: 1 = every pixel of a footprint gets its atomic (same result)
-            PCA_LAUNCH(ctx, PCA_K_RENDER_ZBUFFER, render_zbuffer<true>, dim3(args.G), dim3(RENDER_THREADS), s, args);
+            PCA_LAUNCH(ctx, PCA_K_RENDER_ZBUFFER, render_zbuffer<true>, dim3(args.G), dim3(POINT_THREADS), s, args);
         else
-            PCA_LAUNCH(ctx, PCA_K_RENDER_ZBUFFER, render_zbuffer<false>, dim3(args.G), dim3(RENDER_THREADS), s, args);
+            PCA_LAUNCH(ctx, PCA_K_RENDER_ZBUFFER, render_zbuffer<false>, dim3(args.G), dim3(POINT_THREADS), s, args);
     }
-    PCA_LAUNCH(ctx, PCA_K_RENDER_RESOLVE, render_resolve, dim3((unsigned)((pixels + RENDER_THREADS - 1) / RENDER_THREADS)),
-               dim3(RENDER_THREADS), s, args);
+    PCA_LAUNCH(ctx, PCA_K_RENDER_RESOLVE, render_resolve, dim3((unsigned)((pixels + POINT_THREADS - 1) / POINT_THREADS)),
+               dim3(POINT_THREADS), s, args);
     PCA_CHECK(ctx, hipGetLastError());
     return 0;
 }

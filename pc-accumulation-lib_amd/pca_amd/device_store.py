@@ -609,16 +609,17 @@ class DeviceStore:
             ws[0] = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
         return ws[0]
 
-    def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None):
+    def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None, writes=False):
         """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
-        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, bev_voxel_instances, render_camera -- whose `prm` is its camera block; the next pass
-        of the family starts here): last_frame's default,
-        the bound at which the window is cut (max_points; default: the live window's own) and -- side = (name,
-        pca_*_workspace_bytes) -- the pass's scratch.  Returns (last_frame, max_points, call).
-        call(fn, own, outs, split_frame=None) is the one C call
+        bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, bev_voxel_instances and render_camera, whose `prm`
+        is its camera block; the next pass of the family starts here): last_frame's default, max_points' default (the window's own
+        bound), the scratch for side = (name, pca_*_workspace_bytes) and -- `writes`: the caller stores afterwards, mark_dyn --
+        the owed chain flushed.  Returns (last_frame, max_points, call); call(fn, own, outs, split_frame=None) is the C call
             fn(ctx, store, frame_off, slots, max_points, prm, *own, owed chain, [workspace], *outs' pointers, stream)
         with the owed chain taken read-only from bev_pending (which flushes it when the window does not cover what is owed).
         The C call runs a noted K1 first: after it nothing is noted any more; a refused call raises and leaves it noted."""
+        if writes:
+            self.flush_pending()
         last_frame = self.n_frames if last_frame is None else last_frame
         max_points = self.max_window_points() if max_points is None else max(int(max_points), 1)
         ws = None if side is None else self._side_workspace(*side, max_points, int(prm.px))
@@ -633,6 +634,14 @@ class DeviceStore:
                          *(None if t is None else t.data_ptr() for t in outs), ctx.stream()))
             self._k1_noted = None
         return last_frame, max_points, call
+
+    def _window_extent(self, first_frame, last_frame, max_points, per_point):
+        """(first point, per_point[:exact length, cut at max_points]) of live frames [first_frame, last_frame): one synchronising read-back."""
+        lo, hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].tolist()
+        return lo, per_point[:min(hi - lo, max_points)]
+
+    def _mark_dyn(self, lo, flags):
+        self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
 
     def bev_class_planes(self, split_frame, prm, groups, first_frame=0, last_frame=None, want_counts=False):
         """Planes of any semantic class groups over live frames [first_frame, last_frame), 'present' = frames before
@@ -669,9 +678,7 @@ class DeviceStore:
         mark is made in THIS view's cells and persists: every later raster, of any view, treats these points as dynamic.
         max_points: the bound at which the window is cut (default: the live window's own bound)."""
         lib = self.ctx.lib
-        if mark_dyn:
-            self.flush_pending()                       # a call that must write: nothing stays owed
-        last_frame, max_points, call = self._window_pass(prm, first_frame, last_frame, max_points,
+        last_frame, max_points, call = self._window_pass(prm, first_frame, last_frame, max_points, writes=mark_dyn,
                                                          side=('elev', lib.pca_bev_elev_workspace_bytes))
         side = max(int(prm.px), 1)
         elev = torch.empty((side, side), dtype=torch.float64, device=self.device)
@@ -679,11 +686,9 @@ class DeviceStore:
         flags = torch.empty(max_points, dtype=torch.uint8, device=self.device)
         counts = torch.empty(3, dtype=torch.int64, device=self.device)
         call(lib.pca_bev_elev_partition, (float(elev_thresh), 1 if include_dyn else 0), (elev, obs, flags, counts))
-        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
-        lo, n = int(lo_hi[0]), min(int(lo_hi[1] - lo_hi[0]), max_points)
-        flags = flags[:n]
+        lo, flags = self._window_extent(first_frame, last_frame, max_points, flags)
         if mark_dyn:
-            self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
+            self._mark_dyn(lo, flags)
         return {'elev': elev, 'observed': obs.bool(), 'flags': flags, 'counts': counts}
 
     def bev_voxel_labels(self, prm, z_lo, z_step, nz, label_of, n_labels, first_frame=0, last_frame=None, include_dyn=False,
@@ -767,11 +772,9 @@ class DeviceStore:
         lib = self.ctx.lib
         if not 0 <= int(min_cross) < 1 << 32 or not -(1 << 31) <= int(end_margin) < 1 << 31:
             raise ValueError('min_cross must fit an unsigned, end_margin a signed 32-bit integer')
-        if mark_dyn:
-            self.flush_pending()                       # a call that must write: nothing stays owed
         nz = int(nz)
         last_frame, max_points, call = self._window_pass(
-            prm, first_frame, last_frame, max_points,
+            prm, first_frame, last_frame, max_points, writes=mark_dyn,
             side=('carve', lambda m, px: lib.pca_bev_carve_workspace_bytes(m, px, nz)))
         org = self._origins_of(origins, last_frame - first_frame)
         only = _lib.PcaClassGroup()
@@ -784,11 +787,9 @@ class DeviceStore:
         stats = torch.empty(6, dtype=torch.int64, device=self.device)
         call(lib.pca_bev_voxel_carve, (float(z_lo), float(z_step), nz, 1 if include_dyn else 0, org.data_ptr(), only,
                                        int(end_margin), int(min_cross), float(ratio)), (hits, cross, flags, stats))
-        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
-        lo, n = int(lo_hi[0]), min(int(lo_hi[1] - lo_hi[0]), max_points)
-        flags = flags[:n]
+        lo, flags = self._window_extent(first_frame, last_frame, max_points, flags)
         if mark_dyn:
-            self.dyn[lo + torch.nonzero(flags == 1).squeeze(1)] = 1
+            self._mark_dyn(lo, flags)
         return {'hits': hits, 'cross': cross, 'flags': flags, 'stats': stats}
 
     def bev_voxel_instances(self, prm, z_lo, z_step, nz, label_of, n_labels, min_points=1, connectivity=26, min_voxels=1,
@@ -833,11 +834,10 @@ class DeviceStore:
         call(lib.pca_bev_voxel_instances, (float(z_lo), float(z_step), nz, label_table.ctypes.data, n_labels, _lib.DYN_MODES[dyn],
                                            min_points, connectivity, min_voxels, max_instances),
              (inst, ids, table, label_counts, stats))
-        lo_hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].cpu()
-        n = min(int(lo_hi[1] - lo_hi[0]), max_points)
+        _, ids = self._window_extent(first_frame, last_frame, max_points, ids)
         # the first maximum is the smallest label of a tie
         top_label = torch.where(label_counts.sum(dim=1) > 0, label_counts.argmax(dim=1), 255).to(torch.uint8)
-        return {'inst': inst, 'ids': ids[:n], 'table': table, 'label_counts': label_counts, 'top_label': top_label, 'stats': stats}
+        return {'inst': inst, 'ids': ids, 'table': table, 'label_counts': label_counts, 'top_label': top_label, 'stats': stats}
 
     def render_camera(self, cam, first_frame=0, last_frame=None, classes=None, max_points=None):
         """The stored points of the live frames [first_frame, last_frame) rendered into a pinhole camera with a z-buffer
