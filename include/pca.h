@@ -672,6 +672,54 @@ int pca_render_camera(pca_ctx *ctx, const pca_store *store, const int64_t *frame
                       void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Camera rays cast through the voxel grid of pca_bev_voxel_labels: which voxels a pinhole camera sees before its ray is
+ *       stopped by an occupied voxel -- the "mask_camera" of Occ3D, the ".occluded" of SemanticKITTI-SSC / SSCBench-KITTI-360,
+ *       beside the lidar mask of pca_bev_voxel_rays -- and, per ray, the first occupied voxel, its depth and its label.  No
+ *       reference counterpart.  One ray per pixel of the (strided) image; occupied is whatever `labels` says (!= 255).
+ *     Everything is f64, each operation rounded on its own, nothing fused, the divisions IEEE.
+ *     The camera: with P = [M | p4] from store coordinates to the image (as pca_render_camera takes it), the host passes
+ *       Minv = inv(M) (row-major 3x3) and C = -Minv p4, the camera centre.  The call never sees P: its results are defined on
+ *       Minv and C, however the host got them.
+ *     The rays: nu = width / stride, nv = height / stride (integer division).  Ray (i, j), 0 <= i < nu, 0 <= j < nv, goes
+ *       through the pixel position u = i stride + (stride - 1) / 2.0, v = j stride + (stride - 1) / 2.0 (pixel centres sit at
+ *       integer coordinates, as in K1 and pca_render_camera); its outputs sit at [j][i].
+ *       dir_k = (Minv[3k] u + Minv[3k+1] v) + Minv[3k+2];  start S = C;  end E_k = C_k + max_depth dir_k, the point at camera
+ *       depth max_depth (no square root).
+ *     Grid coordinates s, e of S, E and the voxel of a position: word for word those of pca_bev_voxel_rays, from the same
+ *       code.  A ray with a coordinate of s or e that is not finite or is >= 2^30 in magnitude is dropped (stats[2]); with
+ *       start voxel c, end voxel g and n_a = |g_a - c_a|, a ray with N = n_0 + n_1 + n_2 > PCA_BEV_RAYS_MAX_STEPS is dropped
+ *       (stats[3]).
+ *     The walk: set-up, step and tie order (u, v, w) are those of pca_bev_voxel_rays; the ray visits N + 1 voxels c_0 .. c_N
+ *       -- unlike a lidar ray, the end voxel counts.  For each visited voxel (i, j, k) inside the grid, in order:
+ *       visible[k][px - 1 - j][i] = 1; if labels there is not 255 the ray has HIT: it records the voxel and stops.
+ *       t_enter is 0.0 for c_0, else the tMax of the axis that was just stepped, taken before its increment.
+ *     Per ray (dev [nv][nu], each may be NULL): hit i32 = the place (k px + (px - 1 - j)) px + i of the hit voxel, -1 without
+ *       a hit (a dropped ray included); depth f32 = (float)(t_enter max_depth) of the hit, 0 without; label u8 = labels at
+ *       the hit, 255 without.
+ *     visible u8 [nz][px][px]: cam->clear != 0: zeroed first; cam->clear == 0: the call marks into what is there (the union
+ *       over several cameras).  Every writer writes 1: the result does not depend on any order.
+ *     stats i64 [5], zeroed on every call: rays, rays cast (not dropped), dropped not finite, dropped too long, hits.
+ *     Scope: ONE pinhole per call; no lens distortion; whether a voxel stops a ray is decided by `labels` alone.
+ *     Of prm, origin, R (a rotation about z, checked), dx, dy, view and px are read.
+ *     Limits: prm, labels, cam, visible and stats not NULL; width, height, stride >= 1, stride <= min(width, height);
+ *       max_depth finite and > 0; every entry of Minv and C finite; 1 <= nz <= 32, z_lo finite, z_step finite and > 0;
+ *       1 <= px <= 1024.  No workspace.
+ *     The call reads neither the store nor the owed chain and writes only its outputs.  Every argument is checked before
+ *     anything is launched or cleared; -1 with pca_last_error set ("bev voxel camera: ..." naming the argument).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    double Minv[9], C[3];      /* inv(M) row-major and the camera centre -inv(M) p4, for P = [M | p4] */
+    int32_t width, height, stride, clear;
+    double max_depth;
+} pca_ray_camera;
+int pca_bev_voxel_camera(pca_ctx *ctx, const pca_bev_params *prm, double z_lo, double z_step, int nz,
+                         const uint8_t *labels /*dev [nz][px][px], 255 = empty*/, const pca_ray_camera *cam,
+                         uint8_t *visible /*dev [nz][px][px]*/,
+                         int32_t *hit /*dev [nv][nu] or NULL*/, float *depth /*dev [nv][nu] or NULL*/, uint8_t *label /*dev [nv][nu] or NULL*/,
+                         int64_t *stats /*dev [5]: rays, cast, dropped not finite, dropped too long, hits*/,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -1013,10 +1061,11 @@ enum {
     PCA_K_BEV_VOXEL_BIN, PCA_K_BEV_VOXEL_CELLS, PCA_K_BEV_VOXEL_RAYS, PCA_K_RENDER_ZBUFFER, PCA_K_RENDER_RESOLVE,
     PCA_K_BEV_CARVE_ENDS, PCA_K_BEV_CARVE_RAYS, PCA_K_BEV_CARVE_FLAGS, PCA_K_COUNT
 };
-/* The ids that follow (the first block above is closed: its length is pinned): the kernels of pca_bev_voxel_instances. */
+/* The ids that follow (the first block above is closed: its length is pinned): the kernels of pca_bev_voxel_instances, then
+ * the one of pca_bev_voxel_camera. */
 enum {
     PCA_K_BEV_INST_INIT = PCA_K_COUNT, PCA_K_BEV_INST_MERGE, PCA_K_BEV_INST_COMPRESS, PCA_K_BEV_INST_SUMS, PCA_K_BEV_INST_OFFSETS,
-    PCA_K_BEV_INST_NUMBER, PCA_K_BEV_INST_WRITE, PCA_K_BEV_INST_POINTS, PCA_K_TOTAL
+    PCA_K_BEV_INST_NUMBER, PCA_K_BEV_INST_WRITE, PCA_K_BEV_INST_POINTS, PCA_K_BEV_CAMERA_RAYS, PCA_K_TOTAL
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

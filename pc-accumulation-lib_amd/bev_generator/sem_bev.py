@@ -380,6 +380,22 @@ class SemBEVGenerator(BEVGenerator):
         st, prm, frames = self._one_set_pass(pc, 'rays', rot_mat, dx, dy, aug_view_size, per_frame=True)
         return st.bev_voxel_rays(prm, *grid, origins, include_dyn=include_dyn, **frames)
 
+    # ---- camera rays through the voxel grid: visible against occluded (extension: pca_bev_voxel_camera) ------------
+    def voxel_camera_device(self, pc, labels, cams, rot_mat, dx, dy, aug_view_size, z_range, nz, stride=1, max_depth=None):
+        """One ray per pixel of every camera of `cams`, cast through the grid of voxel_labels_device (same frame, same
+        z_range and nz) until the first voxel that `labels` (uint8 [nz, px, px], 255 = empty; a cuda tensor or a numpy
+        array) calls occupied: DeviceStore.bev_voxel_camera's dict of cuda tensors 'visible' (uint8 [nz, px, px]), the
+        per-camera lists 'hit', 'depth', 'label' and 'stats' (int64 [cameras, 5]).  cams: a list of (P 3x4, (W, H)).  pc
+        names the frame the cameras live in and is not read: a WindowPart -- P from the store's coordinates to the image --
+        or None -- P from BEV-frame metres to the image.  max_depth: the camera depth at which a ray ends; None:
+        aug_view_size, the side of the grid.  One pinhole per call, no lens distortion."""
+        grid = self._voxel_grid(z_range, nz)
+        if pc is not None and not isinstance(pc, WindowPart):
+            raise ValueError('voxel_camera_device: pc is a WindowPart or None (the rays read labels, not points)')
+        prm = self._pass_params(pc, rot_mat, dx, dy, aug_view_size)
+        st = pc.window.store if isinstance(pc, WindowPart) else self._tmp_store('camera')
+        return st.bev_voxel_camera(prm, *grid, labels, cams, stride=stride, max_depth=max_depth)
+
     # ---- free-space carving: points that beams saw through are dynamic (extension: pca_bev_voxel_carve) ------------
     def dynamic_classes(self):
         """The classes that can move: sem_idxs' car, truck, bus and motorcycle (those the dynamic plane is made of)."""

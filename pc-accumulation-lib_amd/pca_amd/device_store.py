@@ -871,6 +871,51 @@ class DeviceStore:
         call(self.ctx.lib.pca_render_camera, (only, ), (keys, depth, index, rgb, sem, stats))
         return {'depth': depth, 'index': index, 'rgb': rgb, 'sem': sem, 'stats': stats}
 
+    def bev_voxel_camera(self, prm, z_lo, z_step, nz, labels, cams, stride=1, max_depth=None):
+        """Camera rays cast through the voxel grid of bev_voxel_labels (pca_bev_voxel_camera): one ray per pixel of every
+        camera, from the camera centre to camera depth max_depth (None: prm.view, the side of the grid); a ray marks the voxels it visits and stops at the first
+        occupied one.  labels: uint8 [nz, px, px], a cuda tensor or a numpy array (uploaded), 255 = empty -- occupied is
+        whatever it says.  cams: a list of (P, (W, H)), P 3x4 from the coordinates of `prm` (the store's) to the image, as
+        render_camera takes it; inv(M) and the camera centre of P = [M | p4] are computed in numpy f64
+        (_lib.make_ray_camera).  stride: every stride-th pixel casts a ray, through the middle of its stride x stride block.
+        The cameras run one call each into the same 'visible' (the first clears it).  One pinhole per call, no lens
+        distortion.
+        Returns a dict of cuda tensors: 'visible' uint8 [nz, px, px], image rows, 1 = a ray of some camera reached the voxel
+        (the voxel that stopped it included); 'hit' int32, 'depth' float32, 'label' uint8: lists with one [H // stride,
+        W // stride] tensor per camera -- the place (k px + row) px + col of the first occupied voxel (-1: none), its camera
+        depth (0: none) and its label (255: none); 'stats' int64 [cameras, 5]: rays, rays cast, dropped for a coordinate
+        that is not finite (or beyond 2^30), dropped for more than 16 384 voxel steps, hits.
+        Neither the store nor the owed re-transforms are read or written."""
+        if not cams:
+            raise ValueError('cams must hold at least one (P, (W, H))')
+        px, nz = int(prm.px), int(nz)
+        max_depth = float(prm.view) if max_depth is None else float(max_depth)
+        shape = (max(nz, 1), max(px, 1), max(px, 1))
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8))
+        labels = labels.to(device=self.device).contiguous()
+        if labels.dtype != torch.uint8 or tuple(labels.shape) != shape:
+            raise ValueError('labels must be uint8 [nz, px, px]')
+        ctx = self.ctx
+        visible = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        stats = torch.empty((len(cams), 5), dtype=torch.int64, device=self.device)
+        out = {'visible': visible, 'hit': [], 'depth': [], 'label': [], 'stats': stats}
+        for n, (P, size) in enumerate(cams):
+            cam = _lib.make_ray_camera(P, size[0], size[1], stride, max_depth, clear=n == 0)
+            # (a size or stride the call refuses: nothing to allocate for it)
+            ok = cam.stride >= 1 and cam.width >= cam.stride and cam.height >= cam.stride
+            rays = (cam.height // cam.stride, cam.width // cam.stride) if ok else (1, 1)
+            hit = torch.empty(rays, dtype=torch.int32, device=self.device)
+            depth = torch.empty(rays, dtype=torch.float32, device=self.device)
+            label = torch.empty(rays, dtype=torch.uint8, device=self.device)
+            ctx.check(ctx.lib.pca_bev_voxel_camera(ctx.h, C.byref(prm), float(z_lo), float(z_step), nz, labels.data_ptr(),
+                                                   C.byref(cam), visible.data_ptr(), hit.data_ptr(), depth.data_ptr(),
+                                                   label.data_ptr(), stats[n].data_ptr(), ctx.stream()))
+            out['hit'].append(hit)
+            out['depth'].append(depth)
+            out['label'].append(label)
+        return out
+
     def bev_many(self, jobs, out16):
         """jobs: [(split_frame, prm, first_frame, last_frame | None)]; out16: cuda float16 [len(jobs),21,px,px].  All rasters
         in ONE launch of each kernel (pca_bev_generate_many): equal to len(jobs) bev() calls.  Owed transforms are applied

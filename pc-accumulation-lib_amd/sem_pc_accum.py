@@ -380,6 +380,40 @@ class SemanticPointCloudAccumulator:
         out['state'] = torch.where(out['counts'] != 0, 2, out['seen'].to(torch.int32)).to(torch.uint8)
         return out
 
+    def voxel_visibility(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False,
+                         origins=None, cameras=None, stride=1, max_depth=None):
+        """Extension (no reference counterpart): voxel_occupancy of `part` plus the voxels a camera can see -- the
+        'mask_camera' of Occ3D beside its 'mask_lidar' (our 'seen'), the '.occluded' of SemanticKITTI-SSC beside '.invalid' --
+        on the same grid, in the same un-augmented frame.  One ray per pixel of every camera (every stride-th pixel), from
+        the camera centre to camera depth max_depth, through the voxels until the first occupied one; occupied means
+        labels != 255, so the occupancy is whatever voxel_labels says under `classes` and include_dyn.
+        cameras: a list of (P, (W, H)), P 3x4 from the STORE's coordinates to the image, as render_camera takes it; 'visible'
+        is the union over them.  None: the dataset's own camera where the stored coordinates belong to one -- the KITTI class:
+        p_velo_frame and the size of the last integrated image, that is the NEWEST frame's camera, which is the camera of the
+        grid's own moment only for present_idx=None; the base class and NuScenes raise a ValueError.  max_depth: None: the
+        generator's view_size -- the grid is view x view around the ego, so nothing in it lies deeper.  One pinhole per
+        camera and no lens distortion.
+        Returns voxel_occupancy's dict, unchanged, plus DeviceStore.bev_voxel_camera's: 'visible' uint8 [nz, px, px] (1 = a
+        ray reached the voxel, the one that stopped it included); 'hit' int32, 'depth' float32, 'label' uint8, lists with one
+        [H // stride, W // stride] tensor per camera (the first occupied voxel's place, camera depth and label; -1, 0 and 255
+        where the ray hit nothing); 'camera_stats' int64 [cameras, 5] = rays, cast, dropped not finite, dropped too long,
+        hits.  Nothing is written to the store."""
+        gen = self.sem_bev_generator
+        if cameras is None:
+            P, size = self._render_defaults()
+            if P is None or size is None:
+                raise ValueError('voxel_visibility needs cameras: a list of (P 3x4 store coordinates -> image, (W, H))')
+            cameras = [(P, size)]
+        cameras = [(np.asarray(P, dtype=np.float64)[:3], size) for P, size in cameras]
+        out = self.voxel_occupancy(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, include_dyn=include_dyn,
+                                   origins=origins)
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        cam = gen.voxel_camera_device(pc, out['labels'], cameras, rot_mat, 0., 0., view, z_range, nz, stride=stride,
+                                      max_depth=1. * gen.view_size if max_depth is None else max_depth)
+        out['camera_stats'] = cam.pop('stats')
+        out.update(cam)
+        return out
+
     def carve_dynamic(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, end_margin=1, min_cross=2,
                       ratio=1.0, origins=None, mark_dyn=False):
         """Extension (no reference counterpart): free-space carving by ray hit / miss over `part` ('present' | 'future' |
