@@ -720,6 +720,55 @@ int pca_bev_voxel_camera(pca_ctx *ctx, const pca_bev_params *prm, double z_lo, d
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Voxel volumes pooled to coarser scales, and packed into the payloads of SemanticKITTI-SSC's files (pca_voxel_pool.hip).  No
+ *       reference counterpart.  Both calls read volumes in this library's layout -- u8 [nz][px][px], voxel (i, j, k) at
+ *       [k][px - 1 - j][i] -- as pca_bev_voxel_labels, pca_bev_voxel_rays and pca_bev_voxel_camera leave them; neither reads a
+ *       store or points.  Everything is integer.
+ *     Fine voxel state (both calls): OCCUPIED with label l iff its label byte l is < PCA_BEV_VOXEL_MAX_LABELS -- any other byte
+ *       counts as 255, not only 255 itself; else FREE iff its `seen` byte != 0, else UNSEEN.
+ *
+ * pca_voxel_pool: the scales 1:2, 1:4 and 1:8 in ONE launch, one pass over the fine volume.
+ *     A coarse voxel of scale s covers s x s x s fine voxels (k, row, col), aligned at 0; n = s^3.  n_occ, n_free, n_unseen: its
+ *       counts of fine voxels; c_l: the number of its occupied fine voxels with label l -- voxels, not points.
+ *     It is occupied iff n_occ > 0 && n_occ occ_den >= n occ_num (int64 products).  Occupied: labels = the smallest l with c_l
+ *       maximal, state = 2.  Else: labels = 255, state = 1 if n_free > n_unseen, else 0 (a tie is unseen).  visible = 1 iff any
+ *       fine `visible` byte != 0, else 0.  With occ_num / occ_den = 1 / 20 this is the published rule of SemanticKITTI-SSC's
+ *       coarse labels ("more than 0.95 n of the fine voxels empty -> empty"): at least 1, 4 and 26 occupied fine voxels.
+ *     Every scale is decided from the FINE voxels: counts are summed up the hierarchy, decisions never are.
+ *     levels: a HOST array of n_levels (1..3) descriptors; each output dev [nz/s][px/s][px/s] or NULL, not all three NULL.  Every
+ *       byte of every output that is not NULL is written exactly once.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32; scale 2, 4 or 8, none twice; px and nz multiples of every requested scale;
+ *       occ_den >= 1, 0 <= occ_num <= occ_den; labels and seen not NULL; a visible output needs the visible input.
+ *
+ * pca_voxel_pack: the file payloads of ONE level (fine or pooled; px, nz are that level's), one launch.
+ *     The place of voxel (i, j, k) in every output is t = (i px + j) nz + k: SemanticKITTI's order with this grid's (i, j, k) as
+ *       its (x, y, z), z fastest.
+ *     label_out u16 [px px nz], the device's (little-endian) byte order: label_map[l] for an occupied voxel, else empty_value.
+ *     Bit streams, ceil(px px nz / 8) bytes each, exactly numpy's packbits of the bits in t order: bit t is bit 7 - t % 8 of byte
+ *       t / 8, the padding bits of the last byte are 0.  invalid_bits (needs seen): 1 iff UNSEEN.  occluded_bits (needs visible):
+ *       1 iff visible == 0.  bin_bits (needs input_occ): 1 iff input_occ != 0.  Every byte is written exactly once; no atomics.
+ *     Each output may be NULL, not all; label_map: HOST u16 [PCA_BEV_VOXEL_MAX_LABELS], needed by label_out.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32 (no divisibility condition); labels not NULL.
+ *
+ * Both: every argument is checked before anything is launched; -1 with pca_last_error set ("voxel pool: ..." / "voxel pack:
+ *     ..."), nothing written.  PCA_VOXEL_POOL_G / PCA_VOXEL_PACK_G = 1..2048 cap the workgroups.
+ *     Out of scope: votes weighted by point counts; other scales; coarse .occluded / .bin; Occ3D's .npz container; how the fine
+ *     volumes are made; banded grids above 1024.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t scale;             /* 2, 4 or 8 */
+    uint8_t *labels, *state, *visible;     /* dev [nz/scale][px/scale][px/scale], each may be NULL */
+} pca_voxel_pool_level;
+int pca_voxel_pool(pca_ctx *ctx, int px, int nz, const uint8_t *labels /*dev, 255 = no point*/, const uint8_t *seen /*dev*/,
+                   const uint8_t *visible /*dev or NULL*/, int occ_num, int occ_den,
+                   const pca_voxel_pool_level *levels /*host [n_levels]*/, int n_levels, void *stream);
+int pca_voxel_pack(pca_ctx *ctx, int px, int nz, const uint8_t *labels /*dev*/, const uint8_t *seen /*dev or NULL*/,
+                   const uint8_t *visible /*dev or NULL*/, const uint8_t *input_occ /*dev or NULL*/,
+                   const uint16_t *label_map /*host [32]*/, uint16_t empty_value,
+                   uint16_t *label_out /*dev or NULL*/, uint8_t *invalid_bits /*dev or NULL*/, uint8_t *occluded_bits /*dev or NULL*/,
+                   uint8_t *bin_bits /*dev or NULL*/, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -1066,6 +1115,10 @@ enum {
 enum {
     PCA_K_BEV_INST_INIT = PCA_K_COUNT, PCA_K_BEV_INST_MERGE, PCA_K_BEV_INST_COMPRESS, PCA_K_BEV_INST_SUMS, PCA_K_BEV_INST_OFFSETS,
     PCA_K_BEV_INST_NUMBER, PCA_K_BEV_INST_WRITE, PCA_K_BEV_INST_POINTS, PCA_K_BEV_CAMERA_RAYS, PCA_K_TOTAL
+};
+/* A third block (the second is closed too): the kernels of pca_voxel_pool and pca_voxel_pack.  The profiler's tables end here. */
+enum {
+    PCA_K_VOXEL_POOL = PCA_K_TOTAL, PCA_K_VOXEL_PACK, PCA_K_END
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

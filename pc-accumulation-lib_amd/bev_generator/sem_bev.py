@@ -353,17 +353,17 @@ class SemBEVGenerator(BEVGenerator):
                 table[c] = label
         return table, len(classes)
 
-    def voxel_labels_device(self, pc, rot_mat, dx, dy, aug_view_size, z_range, nz, classes=None, include_dyn=False):
+    def voxel_labels_device(self, pc, rot_mat, dx, dy, aug_view_size, z_range, nz, classes=None, include_dyn=False, keep_owed=False):
         """One point set voxelised into semantic occupancy labels, in the frame the 21 planes are rasterised in, with nz
         height bins over z_range = (lo, hi) metres of that frame (DeviceStore.bev_voxel_labels: the dict of cuda tensors
         'labels', 'counts', 'top', each [nz, px, px]).  pc: a WindowPart or host rows in BEV-frame metres.  classes: see
-        voxel_label_table (sem_idxs names are taken too)."""
+        voxel_label_table (sem_idxs names are taken too).  keep_owed: see DeviceStore.bev_voxel_labels."""
         grid = self._voxel_grid(z_range, nz)
         if classes is not None:
             classes = [self._classes_of(g) for g in classes]
         table, n_labels = self.voxel_label_table(classes)
         st, prm, frames = self._one_set_pass(pc, 'voxel', rot_mat, dx, dy, aug_view_size)
-        return st.bev_voxel_labels(prm, *grid, table, n_labels, include_dyn=include_dyn, **frames)
+        return st.bev_voxel_labels(prm, *grid, table, n_labels, include_dyn=include_dyn, keep_owed=keep_owed, **frames)
 
     # ---- rays through the voxel grid: free against unseen (extension: pca_bev_voxel_rays) ------------
     def voxel_rays_device(self, pc, origins, rot_mat, dx, dy, aug_view_size, z_range, nz, include_dyn=False):
@@ -395,6 +395,40 @@ class SemBEVGenerator(BEVGenerator):
         prm = self._pass_params(pc, rot_mat, dx, dy, aug_view_size)
         st = pc.window.store if isinstance(pc, WindowPart) else self._tmp_store('camera')
         return st.bev_voxel_camera(prm, *grid, labels, cams, stride=stride, max_depth=max_depth)
+
+    # ---- coarser scales and SSC file payloads of the volumes (extension: pca_voxel_pool, pca_voxel_pack) ------------
+    def voxel_pyramid_device(self, labels, seen, visible=None, input_occ=None, scales=(1, 2, 4, 8), label_map=None, empty_value=0,
+                             occupied_fraction=(1, 20)):
+        """The volumes of voxel_labels_device / voxel_rays_device / voxel_camera_device (uint8 [nz, px, px], cuda tensors or
+        numpy arrays) as the scales SemanticKITTI-SSC ships, with each level's file payloads: ONE pool call for the scales
+        above 1 (DeviceStore.voxel_pool; every scale is decided from the fine voxels), then one pack call per level
+        (DeviceStore.voxel_pack).  Returns {'levels': {s: volumes}, 'packed': {s: payloads}}: level 1 holds the inputs and
+        their 'state' (2 occupied, 1 free, 0 unseen) and is packed into 'label', 'invalid' and, where `visible` / `input_occ`
+        were given, 'occluded' / 'bin'; the pooled levels hold 'labels', 'state' (and 'visible') and are packed into 'label'
+        and 'invalid' only -- the benchmark ships no coarse .occluded / .bin.  label_map, empty_value: see voxel_pack."""
+        import torch
+        st = self._tmp_store('ssc')
+        labels = st._u8_volume(labels, 'labels')
+        shape = tuple(labels.shape)
+        seen = st._u8_volume(seen, 'seen', shape)
+        visible = None if visible is None else st._u8_volume(visible, 'visible', shape)
+        input_occ = None if input_occ is None else st._u8_volume(input_occ, 'input_occ', shape)
+        scales = [int(s) for s in scales]
+        levels, packed = {}, {}
+        pooled = st.voxel_pool(labels, seen, visible, [s for s in scales if s != 1], occupied_fraction) if scales != [1] else {}
+        for s in scales:
+            if s == 1:
+                occ = labels < 32
+                state = torch.where(occ, 2, (seen != 0).to(torch.int32)).to(torch.uint8)
+                levels[1] = {'labels': labels, 'seen': seen, 'state': state}
+                levels[1].update({} if visible is None else {'visible': visible})
+                levels[1].update({} if input_occ is None else {'input_occ': input_occ})
+                packed[1] = st.voxel_pack(labels, seen, visible, input_occ, label_map, empty_value)
+            else:
+                levels[s] = pooled[s]
+                # (a pooled level's state is 0 exactly where it is neither occupied nor free: its `seen` for the packer)
+                packed[s] = st.voxel_pack(pooled[s]['labels'], pooled[s]['state'], label_map=label_map, empty_value=empty_value)
+        return {'levels': levels, 'packed': packed}
 
     # ---- free-space carving: points that beams saw through are dynamic (extension: pca_bev_voxel_carve) ------------
     def dynamic_classes(self):

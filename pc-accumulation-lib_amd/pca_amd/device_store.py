@@ -591,6 +591,19 @@ class DeviceStore:
             return 0, None, None, 0
         return n_pend, self._pend_T, self._pend_ends, (1 if n_pend >= self.CHAIN_K else 0)
 
+    def _owed_read_only(self, first_frame, last_frame):
+        """The owed re-transforms as a read-only pass over ANY live frames [first_frame, last_frame) can take them without a
+        flush: a transform owed by the slots below e is owed by the window's slots below min(e, the window's end) -- the C
+        calls refuse an end beyond the window and give a transform whose end lies at or below the window's first slot to no
+        point.  (n_pend, Ts, slot ends, 0); nothing is written back and the chain stays owed."""
+        n_pend, end = 0, self.head + last_frame
+        for T, e in self._pending:
+            if e > self.head:
+                self._pend_T_np[16 * n_pend:16 * n_pend + 16] = T
+                self._pend_ends[n_pend] = min(int(e), end)
+                n_pend += 1
+        return (n_pend, self._pend_T, self._pend_ends, 0) if n_pend else (0, None, None, 0)
+
     def bev_done(self, write_back):
         """After a raster call of this store has returned."""
         if self._pending and write_back:
@@ -609,14 +622,15 @@ class DeviceStore:
             ws[0] = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
         return ws[0]
 
-    def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None, writes=False):
+    def _window_pass(self, prm, first_frame, last_frame, max_points=None, side=None, writes=False, keep_owed=False):
         """What every read-only pass over live frames [first_frame, last_frame) is called with (bev_class_planes,
         bev_elev_partition, bev_voxel_labels, bev_voxel_rays, bev_voxel_carve, bev_voxel_instances and render_camera, whose `prm`
         is its camera block; the next pass of the family starts here): last_frame's default, max_points' default (the window's own
         bound), the scratch for side = (name, pca_*_workspace_bytes) and -- `writes`: the caller stores afterwards, mark_dyn --
         the owed chain flushed.  Returns (last_frame, max_points, call); call(fn, own, outs, split_frame=None) is the C call
             fn(ctx, store, frame_off, slots, max_points, prm, *own, owed chain, [workspace], *outs' pointers, stream)
-        with the owed chain taken read-only from bev_pending (which flushes it when the window does not cover what is owed).
+        with the owed chain taken read-only from bev_pending (which flushes it when the window does not cover what is owed;
+        keep_owed: from _owed_read_only, which never flushes).
         The C call runs a noted K1 first: after it nothing is noted any more; a refused call raises and leaves it noted."""
         if writes:
             self.flush_pending()
@@ -626,7 +640,7 @@ class DeviceStore:
 
         def call(fn, own, outs, split_frame=None):
             ctx = self.ctx
-            n_pend, pend_T, pend_ends, _ = self.bev_pending(first_frame, last_frame)
+            n_pend, pend_T, pend_ends, _ = (self._owed_read_only if keep_owed else self.bev_pending)(first_frame, last_frame)
             slots = [self.head + f for f in (first_frame, split_frame, last_frame) if f is not None]
             st = self.c_store()
             ctx.check(fn(ctx.h, C.byref(st), self.frame_off.data_ptr(), *slots, max_points, C.byref(prm), *own, pend_T, pend_ends,
@@ -692,7 +706,7 @@ class DeviceStore:
         return {'elev': elev, 'observed': obs.bool(), 'flags': flags, 'counts': counts}
 
     def bev_voxel_labels(self, prm, z_lo, z_step, nz, label_of, n_labels, first_frame=0, last_frame=None, include_dyn=False,
-                         max_points=None):
+                         max_points=None, keep_owed=False):
         """Live frames [first_frame, last_frame) voxelised into semantic occupancy labels (pca_bev_voxel_labels): the grid of
         `prm` with nz height bins of z_step metres from z_lo (z in the BEV frame; outside the range a point is dropped, not
         clamped), a majority vote per voxel.  label_of: 256 entries, class -> label below n_labels, 255 = the class takes
@@ -701,13 +715,16 @@ class DeviceStore:
         frequent ones (255: an empty voxel -- free or unseen is not decided here: bev_voxel_rays); 'counts' and 'top'
         int32 holding the u32 numbers of labelled points and of points of the winning label.
         The store is not written: owed re-transforms are applied to what the call reads and stay owed.
-        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        max_points: the bound at which the window is cut (default: the live window's own bound).  keep_owed: a window that
+        does not cover what is owed (it starts behind frame 0 or ends before the newest owing frame) has the owed
+        re-transforms flushed first by default; True leaves the store alone there too."""
         lib = self.ctx.lib
         px = int(prm.px)
         table = np.ascontiguousarray(label_of, dtype=np.uint8)
         if table.shape != (256, ):
             raise ValueError('label_of must hold 256 entries')
-        _, _, call = self._window_pass(prm, first_frame, last_frame, max_points, side=('voxel', lib.pca_bev_voxel_workspace_bytes))
+        _, _, call = self._window_pass(prm, first_frame, last_frame, max_points, side=('voxel', lib.pca_bev_voxel_workspace_bytes),
+                                       keep_owed=keep_owed)
         shape = (max(int(nz), 1), max(px, 1), max(px, 1))
         labels = torch.empty(shape, dtype=torch.uint8, device=self.device)
         counts = torch.empty(shape, dtype=torch.int32, device=self.device)
@@ -914,6 +931,78 @@ class DeviceStore:
             out['hit'].append(hit)
             out['depth'].append(depth)
             out['label'].append(label)
+        return out
+
+    def _u8_volume(self, v, name, shape=None):
+        """A uint8 [nz, px, px] volume on the device (numpy arrays and bool tensors are taken too), checked against `shape`."""
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.ascontiguousarray(v).astype(np.uint8, copy=False))
+        v = v.to(device=self.device)
+        if v.dtype == torch.bool:
+            v = v.to(torch.uint8)
+        v = v.contiguous()
+        if v.dtype != torch.uint8 or v.dim() != 3 or v.shape[1] != v.shape[2] or (shape is not None and tuple(v.shape) != shape):
+            raise ValueError(f'{name} must be uint8 [nz, px, px]' + ('' if shape is None else ', the shape of labels'))
+        return v
+
+    def voxel_pool(self, labels, seen, visible=None, scales=(2, 4, 8), occupied_fraction=(1, 20)):
+        """The volumes of the occupancy chain pooled to coarser scales, all of them in one launch (pca_voxel_pool).  labels,
+        seen, visible (optional): uint8 [nz, px, px], cuda tensors or numpy arrays (uploaded); a voxel is occupied where its
+        label is below 32, else free where seen != 0, else unseen.  scales: any of 2, 4, 8, each dividing px and nz.  A
+        coarse voxel is occupied iff it holds an occupied fine voxel and n_occ * den >= s^3 * num for occupied_fraction =
+        (num, den) -- (1, 20) is SemanticKITTI-SSC's rule -- and takes the smallest label among its most frequent ones (a
+        vote of voxels, taken over the fine voxels at every scale); else it is free iff more of its fine voxels are free
+        than unseen.  Returns {s: {'labels', 'state'[, 'visible']}}, cuda uint8 [nz/s, px/s, px/s]: labels 255 = not
+        occupied, state 2 / 1 / 0 = occupied / free / unseen, visible 1 = some fine voxel was visible.
+        Neither the store nor the owed re-transforms are read or written."""
+        labels = self._u8_volume(labels, 'labels')
+        shape = tuple(labels.shape)
+        seen = self._u8_volume(seen, 'seen', shape)
+        visible = None if visible is None else self._u8_volume(visible, 'visible', shape)
+        nz, px = shape[0], shape[1]
+        scales = [int(s) for s in scales]
+        out = {}
+        levels = (_lib.PcaVoxelPoolLevel * max(len(scales), 1))()
+        for lv, s in zip(levels, scales):
+            # (a scale the call refuses: nothing to allocate for it)
+            coarse = (nz // s, px // s, px // s) if s > 0 and nz >= s and px >= s else (1, 1, 1)
+            vol = {k: torch.empty(coarse, dtype=torch.uint8, device=self.device)
+                   for k in ('labels', 'state') + (('visible', ) if visible is not None else ())}
+            lv.scale, lv.labels, lv.state = s, vol['labels'].data_ptr(), vol['state'].data_ptr()
+            lv.visible = vol['visible'].data_ptr() if visible is not None else None
+            out[s] = vol
+        ctx = self.ctx
+        ctx.check(ctx.lib.pca_voxel_pool(ctx.h, px, nz, labels.data_ptr(), seen.data_ptr(),
+                                         None if visible is None else visible.data_ptr(), int(occupied_fraction[0]),
+                                         int(occupied_fraction[1]), levels, len(scales), ctx.stream()))
+        return out
+
+    def voxel_pack(self, labels, seen=None, visible=None, input_occ=None, label_map=None, empty_value=0):
+        """The file payloads of one level, fine or pooled, in SemanticKITTI-SSC's form (pca_voxel_pack): voxel (i, j, k) of
+        the [nz, px, px] volumes -- at [k, px - 1 - j, i] -- goes to place (i px + j) nz + k.  Returns cuda tensors: 'label'
+        uint16 [px px nz], label_map[l] for an occupied voxel and empty_value elsewhere (label_map: 32 entries; None: l + 1,
+        because label 0 is a class here and 0 means empty in the file); and, one per input that was given, 'invalid' (from
+        seen: 1 = neither occupied nor seen), 'occluded' (from visible: 1 = not visible) and 'bin' (from input_occ: 1 = set)
+        as uint8 [ceil(px px nz / 8)], exactly np.packbits of the bits in place order.  .cpu().numpy().tobytes() of each is
+        the content of the file.  numpy inputs are uploaded."""
+        labels = self._u8_volume(labels, 'labels')
+        shape = tuple(labels.shape)
+        seen, visible, input_occ = (None if v is None else self._u8_volume(v, n, shape)
+                                    for v, n in ((seen, 'seen'), (visible, 'visible'), (input_occ, 'input_occ')))
+        nz, px = shape[0], shape[1]
+        table = np.arange(1, 33, dtype=np.uint16) if label_map is None else np.ascontiguousarray(label_map, dtype=np.uint16)
+        if table.shape != (32, ):
+            raise ValueError('label_map must hold 32 entries')
+        n = px * px * nz
+        out = {'label': torch.empty(n, dtype=torch.uint16, device=self.device)}
+        for key, v in (('invalid', seen), ('occluded', visible), ('bin', input_occ)):
+            if v is not None:
+                out[key] = torch.empty((n + 7) // 8, dtype=torch.uint8, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+        ctx = self.ctx
+        ctx.check(ctx.lib.pca_voxel_pack(ctx.h, px, nz, labels.data_ptr(), ptr(seen), ptr(visible), ptr(input_occ),
+                                         table.ctypes.data, int(empty_value) & 0xffff, out['label'].data_ptr(),
+                                         ptr(out.get('invalid')), ptr(out.get('occluded')), ptr(out.get('bin')), ctx.stream()))
         return out
 
     def bev_many(self, jobs, out16):

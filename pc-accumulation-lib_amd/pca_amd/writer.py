@@ -14,7 +14,10 @@ same splice, smaller files.
 
 submit_preview (PCA_VIZ=device routes viz_bev here) writes a sample's preview sheet as a PNG the same way: the sheet is
 rendered, filtered and compressed on the device (pca_amd/preview.py), once per block of planes; the worker threads assemble
-the container and write the file."""
+the container and write the file.
+
+submit_files writes finished payloads as they are -- the SSC files of pca_amd/ssc.py: a payload that is a cuda tensor leaves
+the device in one asynchronous copy enqueued by the submitting thread, and a worker thread writes the file."""
 import atexit
 import ctypes as C
 import gzip
@@ -247,6 +250,15 @@ class _PreviewItem:
         self.job, self.index, self.path = job, index, path
 
 
+class _FilesItem:
+    """Files whose bytes are final: [(path, bytes-like | pinned host tensor)], and the event behind the copies the pinned
+    tensors are filled by (None: nothing to wait for)."""
+    __slots__ = ('files', 'event')
+
+    def __init__(self, files, event):
+        self.files, self.event = files, event
+
+
 class _Item:
     """One sample on its way through the writer.  job is None: the host codec takes it (bev is a plain dict by the time a
     worker sees it, unless it is the device_only form).  Else: sample `index` of that device job, meta = what
@@ -278,6 +290,8 @@ class AsyncBevWriter:
         self._preview_jobs = {}              # id(planes block) -> its sheet job, while the block lives
         self._parked_preview = None
         self.previews_written = 0
+        self._parked_files = None
+        self.files_written = 0
         self._open = True
         if codec == 'device':
             _device_writers[0] += 1
@@ -330,12 +344,23 @@ class AsyncBevWriter:
         with self._lock:
             self.previews_written += 1
 
+    def _write_files(self, it):
+        for path, data in it.files:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, 'wb') as f:
+                f.write(memoryview(data.numpy()).cast('B') if hasattr(data, 'numpy') else data)
+            with self._lock:
+                self.files_written += 1
+
     def _work(self):
         while True:
             it = self.q.get()
             if it is None:
                 return
             try:
+                if type(it) is _FilesItem:
+                    self._write_files(it)
+                    continue
                 if type(it) is _PreviewItem:
                     self._write_preview(it)
                     continue
@@ -479,6 +504,43 @@ class AsyncBevWriter:
             it.job.wait()
             self.q.put(it)
 
+    # ---- finished payloads (pca_amd/ssc.py)
+    def submit_files(self, files):
+        """files: [(path, payload)], a payload being bytes-like (bytes, bytearray, memoryview, a numpy array) or a tensor.  The
+        copy of every cuda tensor into pinned host memory is enqueued here, on the thread that talks to HIP, on torch's
+        current stream; the item is parked like a sample and released -- waited for and queued -- by the next submit_files,
+        flush or close; the worker threads write the files (counted in files_written).  Payloads without a device tensor
+        are queued at once."""
+        self._release_parked_files()
+        out, copied = [], False
+        for path, data in files:
+            if hasattr(data, 'is_cuda'):
+                import torch
+                flat = data.contiguous().view(-1)
+                if flat.is_cuda:
+                    host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+                    host.copy_(flat, non_blocking=True)
+                    copied = True
+                    flat = host
+                data = flat
+            elif isinstance(data, np.ndarray):
+                data = np.ascontiguousarray(data).tobytes()
+            out.append((str(path), data))
+        if copied:
+            import torch
+            event = torch.cuda.Event()
+            event.record()
+            self._parked_files = _FilesItem(out, event)
+        else:
+            self.q.put(_FilesItem(out, None))
+
+    def _release_parked_files(self):
+        it, self._parked_files = self._parked_files, None
+        if it is not None:
+            it.event.synchronize()
+            it.event = None
+            self.q.put(it)
+
     def _take_refills(self):
         """Samples the workers could not splice: filled in here, on the submitting thread, and queued for the host codec."""
         with self._lock:
@@ -490,6 +552,7 @@ class AsyncBevWriter:
     def flush(self):
         self._release_parked()
         self._release_parked_preview()
+        self._release_parked_files()
         self.q.join()
         while self._take_refills():
             self.q.join()

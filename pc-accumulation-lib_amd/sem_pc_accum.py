@@ -414,6 +414,41 @@ class SemanticPointCloudAccumulator:
         out.update(cam)
         return out
 
+    def voxel_ssc_sample(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False,
+                         origins=None, cameras=None, stride=1, max_depth=None, scales=(1, 2, 4, 8), input_frames=1,
+                         label_map=None, occluded=True):
+        """Extension (no reference counterpart): one semantic-scene-completion sample in SemanticKITTI-SSC's form -- the
+        volumes of voxel_visibility (occluded=True) or, for the classes without a default camera, of voxel_occupancy
+        (occluded=False) of `part`, pooled to `scales` and packed into file payloads on the device
+        (SemBEVGenerator.voxel_pyramid_device).  Returns that dict, unchanged, plus 'input_occ' uint8 [nz, px, px]: 1 where
+        a voxel_labels pass over the last input_frames frames of the PRESENT part -- same frame, grid and classes -- found a
+        point: the single-scan input the benchmark's .bin holds; 'levels': {s: volumes}, level 1 = 'labels', 'seen', 'state'
+        (, 'visible'), 'input_occ', the pooled levels 'labels', 'state' (, 'visible'); 'packed': {s: payloads}, level 1 =
+        'label', 'invalid' (, 'occluded'), 'bin', the pooled levels 'label' and 'invalid'.  label_map: 32 file values, None:
+        label + 1 (0 is 'empty' in the files).  pca_amd.ssc.write_ssc_sample writes the files.
+        Nothing is written to the store."""
+        from bev_generator.bev_generator import DeviceWindow
+        gen = self.sem_bev_generator
+        if int(input_frames) < 1:
+            raise ValueError('input_frames must be >= 1')
+        if occluded:
+            out = self.voxel_visibility(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, include_dyn=include_dyn,
+                                        origins=origins, cameras=cameras, stride=stride, max_depth=max_depth)
+        else:
+            out = self.voxel_occupancy(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, include_dyn=include_dyn,
+                                       origins=origins)
+        pc, rot_mat, view = self._unaugmented_part(present_idx, 'present')
+        lo, hi = pc.frames()
+        w = pc.window
+        scan = DeviceWindow(w.store, hi, w.origin, first=max(lo, hi - int(input_frames)), last=hi).part('full')
+        # (keep_owed: the scan's window does not cover what the older frames owe, and this call writes nothing)
+        one = gen.voxel_labels_device(scan, rot_mat, 0., 0., view, z_range, nz, classes=classes, include_dyn=include_dyn,
+                                      keep_owed=True)
+        out['input_occ'] = (one['counts'] != 0).to(one['labels'].dtype)
+        out.update(gen.voxel_pyramid_device(out['labels'], out['seen'], out.get('visible'), out['input_occ'], scales=scales,
+                                            label_map=label_map))
+        return out
+
     def carve_dynamic(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, end_margin=1, min_cross=2,
                       ratio=1.0, origins=None, mark_dyn=False):
         """Extension (no reference counterpart): free-space carving by ray hit / miss over `part` ('present' | 'future' |
