@@ -769,6 +769,45 @@ int pca_voxel_pack(pca_ctx *ctx, int px, int nz, const uint8_t *labels /*dev*/, 
                    uint8_t *bin_bits /*dev or NULL*/, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact distance transform of a label volume: squared distance, nearest site, its label; fill; TSDF (pca_voxel_distance.hip).
+ *       No reference counterpart.  Volumes in this library's layout -- [nz][px][px], voxel (i, j, k) at [k][px - 1 - j][i]; the
+ *       call reads no store and no points.  The distance is integer arithmetic; only `tsdf` is floating point.
+ *     Sites: a voxel is a site iff its label byte l is < PCA_BEV_VOXEL_MAX_LABELS (any other byte counts as 255, as in
+ *       pca_voxel_pool) and bit l of site_labels is set (site_labels NULL: every label).
+ *     Distance between the places p = (k, row, col) and s = (k', row', col'):
+ *       D(p, s) = w_xy ((row - row')^2 + (col - col')^2) + w_z (k - k')^2, an integer; the two weights express anisotropic voxels
+ *       exactly (cells of 0.3125 m and bins of 0.2 m: 625 : 256 measures metres in units of 0.0125 m).
+ *     Per voxel, the site that minimises the pair (D, q) lexicographically, q = (k' px + row') px + col' the site's linear place:
+ *       a tie in distance goes to the smallest place.  With max_dist2 >= 0, sites with D > max_dist2 do not exist for the voxel.
+ *       dist2 = D, nearest = q, nearest_label = the site's label byte; without a site -1, -1 and 255.  A site has dist2 = 0 and
+ *       nearest = its own place.
+ *     filled: the voxel's own label byte where it is < PCA_BEV_VOXEL_MAX_LABELS (a site or not); else nearest_label where a site
+ *       exists with D <= fill_dist2 and the voxel is eligible -- fill_free != 0, or seen == NULL, or its seen byte is 0 (by default
+ *       a voxel a beam crossed stays free); else 255.
+ *     tsdf, f32, computed in f64 with every operation rounded on its own: m = fmin(sqrt((double)D) * tsdf_unit, tsdf_trunc) /
+ *       tsdf_trunc, m = 1 without a site; v = tsdf_flip ? 1.0 - m : m; sign = -1 where seen != NULL, the voxel's label byte is
+ *       not < PCA_BEV_VOXEL_MAX_LABELS and its seen byte is 0 (unseen), else +1; out = (float)(sign * v).  SSCNet's convention:
+ *       positive in observed space, negative behind surfaces, +-1 at the surface when flipped.
+ *     Each output dev [nz][px][px] or NULL, not all five; every element of every output that is not NULL is written exactly once;
+ *       no atomics; two calls give identical bytes.  workspace: dev, pca_voxel_distance_workspace_bytes(px, nz) bytes (-1 for a
+ *       shape outside the limits), 4-byte aligned.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32; w_xy, w_z >= 1 with w_xy 2 (px-1)^2 + w_z (nz-1)^2 <= 2^31 - 2 (every D fits the
+ *       int32 output); labels not NULL; tsdf needs tsdf_unit and tsdf_trunc finite and > 0; filled needs fill_dist2 >= 0 (< 0: no
+ *       fill).  max_dist2 < 0: unbounded.
+ *     Every argument is checked before anything is launched; -1 with pca_last_error set ("voxel distance: ..."), nothing written.
+ *       Two launches whatever the volume holds.  PCA_VOXEL_DIST_G = 1..2048 caps the workgroups of both.
+ *     Out of scope: distances in float metres for irrational cell ratios; grids above 1024; a .tsdf file; distance to free-space
+ *     boundaries; how the fine volumes are made.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t pca_voxel_distance_workspace_bytes(int px, int nz);
+int pca_voxel_distance(pca_ctx *ctx, int px, int nz, const uint8_t *labels /*dev*/, const uint8_t *seen /*dev or NULL*/,
+                       const pca_class_group *site_labels /*host or NULL = every label*/, int w_xy, int w_z,
+                       int64_t max_dist2 /* <0: unbounded */, int64_t fill_dist2 /* <0: no fill */, int fill_free,
+                       double tsdf_unit, double tsdf_trunc, int tsdf_flip, void *workspace /*dev*/, int64_t workspace_bytes,
+                       int32_t *dist2, int32_t *nearest, uint8_t *nearest_label, uint8_t *filled, float *tsdf /*each dev or NULL, not all*/,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36
  *     (torchvision ToTensor + Normalize on the host): out[c][y][x] = (rgb[y][x][c] / 255 - mean[c]) / std[c] in IEEE f32.
  *     rgb: dev [H,W,3] u8; out: dev [3,H,W] f32.  The CNN itself is an external ONNX file (utils/onnx_utils.py binds this
@@ -1116,9 +1155,13 @@ enum {
     PCA_K_BEV_INST_INIT = PCA_K_COUNT, PCA_K_BEV_INST_MERGE, PCA_K_BEV_INST_COMPRESS, PCA_K_BEV_INST_SUMS, PCA_K_BEV_INST_OFFSETS,
     PCA_K_BEV_INST_NUMBER, PCA_K_BEV_INST_WRITE, PCA_K_BEV_INST_POINTS, PCA_K_BEV_CAMERA_RAYS, PCA_K_TOTAL
 };
-/* A third block (the second is closed too): the kernels of pca_voxel_pool and pca_voxel_pack.  The profiler's tables end here. */
+/* A third block (the second is closed too): the kernels of pca_voxel_pool and pca_voxel_pack. */
 enum {
     PCA_K_VOXEL_POOL = PCA_K_TOTAL, PCA_K_VOXEL_PACK, PCA_K_END
+};
+/* A fourth block (the third is closed as well): the two kernels of pca_voxel_distance.  The profiler's tables end here. */
+enum {
+    PCA_K_VOXEL_DIST_LINES = PCA_K_END, PCA_K_VOXEL_DIST_ROWS, PCA_K_LAST
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

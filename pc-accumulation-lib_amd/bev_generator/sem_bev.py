@@ -430,6 +430,39 @@ class SemBEVGenerator(BEVGenerator):
                 packed[s] = st.voxel_pack(pooled[s]['labels'], pooled[s]['state'], label_map=label_map, empty_value=empty_value)
         return {'levels': levels, 'packed': packed}
 
+    # ---- distance to the nearest labelled voxel: fill, TSDF (extension: pca_voxel_distance) ------------
+    def voxel_distance_device(self, labels, seen, view, z_range, nz, sites=None, metric='metres', max_dist=None, fill_dist=None,
+                              fill_free=False, tsdf_trunc=None, flip=True):
+        """The exact distance transform of the volumes of voxel_labels_device / voxel_rays_device (uint8 [nz, px, px], cuda
+        tensors or numpy arrays; seen may be None) on the grid of side `view` metres with nz height bins over z_range:
+        DeviceStore.voxel_distance's dict of cuda tensors 'dist2', 'nearest', 'nearest_label' (, 'filled' with fill_dist,
+        'tsdf' with tsdf_trunc) plus 'weights' = (w_xy, w_z) and 'unit': sqrt(dist2) * unit is the distance.
+        metric='metres': the weights of pca_amd.host_logic.voxel_metric for this grid's cell and bin, unit in metres, and
+        max_dist / fill_dist / tsdf_trunc in metres; 'voxel': weights (1, 1), unit 1, and they count voxels.  A distance d
+        becomes the integer bound floor((d / unit)^2).  sites: the labels that make a site (None: every label).  flip: the
+        flipped TSDF, 1 at a surface and 0 at tsdf_trunc and beyond."""
+        import math
+
+        from pca_amd import host_logic as hl
+        st = self._tmp_store('ssc')
+        labels = st._u8_volume(labels, 'labels')
+        px = int(labels.shape[1])
+        if metric == 'metres':
+            lo, step, _ = self._voxel_grid(z_range, nz)
+            w_xy, w_z, unit = hl.voxel_metric(float(view) / px, step, px=px, nz=int(labels.shape[0]))
+        elif metric == 'voxel':
+            w_xy, w_z, unit = 1, 1, 1.
+        else:
+            raise ValueError("metric must be 'metres' or 'voxel'")
+
+        def bound(d):
+            return None if d is None else int(min(math.floor((float(d) / unit) ** 2), 2 ** 31 - 1))
+        out = st.voxel_distance(labels, seen, site_labels=sites, weights=(w_xy, w_z), max_dist2=bound(max_dist),
+                                fill_dist2=bound(fill_dist), fill_free=fill_free,
+                                tsdf=None if tsdf_trunc is None else (unit, float(tsdf_trunc), flip))
+        out['weights'], out['unit'] = (w_xy, w_z), unit
+        return out
+
     # ---- free-space carving: points that beams saw through are dynamic (extension: pca_bev_voxel_carve) ------------
     def dynamic_classes(self):
         """The classes that can move: sem_idxs' car, truck, bus and motorcycle (those the dynamic plane is made of)."""

@@ -23,7 +23,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
            'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
-           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
+           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_voxel_distance_workspace_bytes', 'pca_voxel_distance', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
            'pca_host_track_poses', 'pca_host_track_segments', 'pca_host_track_set', 'pca_host_track_transform',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
@@ -43,6 +43,7 @@ KERNEL_IDS_INST = ('bev_inst_init', 'bev_inst_merge', 'bev_inst_compress', 'bev_
                    'bev_inst_write', 'bev_inst_points')   # ... and, in pca.h's second enum block, those of pca_bev_voxel_instances
 KERNEL_IDS_CAMERA = ('bev_camera_rays', )                      # ... and the one of pca_bev_voxel_camera
 KERNEL_IDS_SSC = ('voxel_pool', 'voxel_pack')                  # ... and, in the third block, pca_voxel_pool's and pca_voxel_pack's
+KERNEL_IDS_DIST = ('voxel_dist_lines', 'voxel_dist_rows')      # ... and, in the fourth block, the two of pca_voxel_distance
 BEV_INST_COLS = 9
 DYN_MODES = {'static': 0, 'all': 1, 'dynamic': 2}
 BEV_EXTRA_PLANES = ('elevation_max', 'elevation_mean', 'intensity_mean')
@@ -265,6 +266,10 @@ def load():
                                          vp, vp, vp, vp, vp, vp]
     lib.pca_voxel_pool.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(PcaVoxelPoolLevel), i32, vp]
     lib.pca_voxel_pack.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint16, vp, vp, vp, vp, vp]
+    lib.pca_voxel_distance_workspace_bytes.argtypes = [i32, i32]
+    lib.pca_voxel_distance_workspace_bytes.restype = i64
+    lib.pca_voxel_distance.argtypes = [vp, i32, i32, vp, vp, C.POINTER(PcaClassGroup), i32, i32, i64, i64, i32, C.c_double, C.c_double,
+                                       i32, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.pca_bev_warp.argtypes = [vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.pca_voxel_dedup_workspace_bytes.restype = C.c_int64
     lib.pca_voxel_dedup_workspace_bytes.argtypes = [i64, i32]
@@ -422,7 +427,7 @@ class Context:
     def profile_read(self):
         """{kernel name: (total_ms, launches)} since profiling was enabled (synchronises)."""
         out = {}
-        for k, name in enumerate(KERNEL_IDS + KERNEL_IDS_VOXEL + KERNEL_IDS_RAYS + KERNEL_IDS_RENDER + KERNEL_IDS_CARVE + KERNEL_IDS_INST + KERNEL_IDS_CAMERA + KERNEL_IDS_SSC):
+        for k, name in enumerate(KERNEL_IDS + KERNEL_IDS_VOXEL + KERNEL_IDS_RAYS + KERNEL_IDS_RENDER + KERNEL_IDS_CARVE + KERNEL_IDS_INST + KERNEL_IDS_CAMERA + KERNEL_IDS_SSC + KERNEL_IDS_DIST):
             ms, n = C.c_double(0), C.c_int64(0)
             self.check(self.lib.pca_profile_read(self.h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)

@@ -58,6 +58,7 @@ class DeviceStore:
         self._ws_side = {}
         self._render_keys = {}           # (H, W) -> the z-buffer's keys (render_camera)
         self._dedup_ws = None
+        self._dist_ws = None              # pca_voxel_distance's scratch, grown to the largest volume seen
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
         self._pend_T = (C.c_double * (16 * self.CHAIN_MAX))()      # the owed chain as the C calls take it
@@ -1003,6 +1004,50 @@ class DeviceStore:
         ctx.check(ctx.lib.pca_voxel_pack(ctx.h, px, nz, labels.data_ptr(), ptr(seen), ptr(visible), ptr(input_occ),
                                          table.ctypes.data, int(empty_value) & 0xffff, out['label'].data_ptr(),
                                          ptr(out.get('invalid')), ptr(out.get('occluded')), ptr(out.get('bin')), ctx.stream()))
+        return out
+
+    def voxel_distance(self, labels, seen=None, site_labels=None, weights=(1, 1), max_dist2=None, fill_dist2=None, fill_free=False,
+                       tsdf=None):
+        """The exact distance transform of a label volume (pca_voxel_distance): how far every voxel is from the nearest site,
+        which site that is, and what is made of it.  labels, seen (optional): uint8 [nz, px, px], cuda tensors or numpy arrays
+        (uploaded).  A voxel is a site where its label is below 32 and in site_labels (an iterable of labels; None: every
+        label).  The squared distance between two places is weights[0] (drow^2 + dcol^2) + weights[1] dk^2, in integers
+        (pca_amd.host_logic.voxel_metric gives the weights of a grid in metres); of equally near sites the one with the
+        smallest place (k px + row) px + col wins.  max_dist2: sites further than that do not exist (None: unbounded).
+        Returns a dict of cuda tensors [nz, px, px]: 'dist2' int32 (-1: no site), 'nearest' int32 (the site's place, -1),
+        'nearest_label' uint8 (255); with fill_dist2, 'filled' uint8: the own label where there is one, else the nearest
+        site's label where it lies within fill_dist2 and the voxel is unseen (seen == 0; every empty voxel with fill_free
+        or without `seen`), else 255; with tsdf = (unit, trunc, flip), 'tsdf' float32: min(sqrt(dist2) unit, trunc) / trunc
+        (1 without a site), 1 - that if flip, negative where the voxel is empty and unseen.
+        Neither the store nor the owed re-transforms are read or written."""
+        labels = self._u8_volume(labels, 'labels')
+        shape = tuple(labels.shape)
+        seen = None if seen is None else self._u8_volume(seen, 'seen', shape)
+        nz, px = shape[0], shape[1]
+        ctx = self.ctx
+        need = int(ctx.lib.pca_voxel_distance_workspace_bytes(px, nz))
+        if need > 0 and (self._dist_ws is None or self._dist_ws.numel() < need):
+            self._dist_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._dist_ws
+        group = None
+        if site_labels is not None:
+            group = _lib.PcaClassGroup()
+            group.mask[:] = list(_lib.class_mask(site_labels))
+        out = {'dist2': torch.empty(shape, dtype=torch.int32, device=self.device),
+               'nearest': torch.empty(shape, dtype=torch.int32, device=self.device),
+               'nearest_label': torch.empty(shape, dtype=torch.uint8, device=self.device)}
+        if fill_dist2 is not None:
+            out['filled'] = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        unit, trunc, flip = (0., 0., False) if tsdf is None else tsdf
+        if tsdf is not None:
+            out['tsdf'] = torch.empty(shape, dtype=torch.float32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+        ctx.check(ctx.lib.pca_voxel_distance(ctx.h, px, nz, labels.data_ptr(), ptr(seen), None if group is None else C.byref(group),
+                                             int(weights[0]), int(weights[1]), -1 if max_dist2 is None else int(max_dist2),
+                                             -1 if fill_dist2 is None else int(fill_dist2), 1 if fill_free else 0, float(unit),
+                                             float(trunc), 1 if flip else 0, ptr(ws), 0 if ws is None else ws.numel(),
+                                             out['dist2'].data_ptr(), out['nearest'].data_ptr(), out['nearest_label'].data_ptr(),
+                                             ptr(out.get('filled')), ptr(out.get('tsdf')), ctx.stream()))
         return out
 
     def bev_many(self, jobs, out16):

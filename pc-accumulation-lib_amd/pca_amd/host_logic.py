@@ -424,6 +424,31 @@ def instance_boxes(table, n, view, px, z_lo, z_step):
     return out
 
 
+def voxel_metric(cell, z_step, max_den=64, px=None, nz=None):
+    """(w_xy, w_z, unit) of DeviceStore.voxel_distance for a grid with cells of `cell` metres and height bins of `z_step`
+    metres: a / b = Fraction(cell / z_step).limit_denominator(max_den), w_xy = a^2, w_z = b^2, unit = cell / a, so that
+    sqrt(dist2) * unit is metres -- the default grid (0.3125 m, 0.2 m) gives (625, 256, 0.0125) exactly.  A ratio that no
+    fraction with a denominator up to max_den meets exactly (an irrational one, say) is still served by the nearest such
+    fraction: in the plane `unit` is exact, along z a bin then counts as b * unit metres instead of z_step -- the returned
+    unit says what the numbers mean, nothing is measured in float metres.  With px and nz given, weights beyond the call's
+    limit w_xy 2 (px-1)^2 + w_z (nz-1)^2 <= 2^31 - 2 raise a ValueError (lower max_den); without them the caller checks."""
+    from fractions import Fraction
+    cell, z_step = float(cell), float(z_step)
+    if not (cell > 0 and z_step > 0 and math.isfinite(cell) and math.isfinite(z_step)):
+        raise ValueError('voxel_metric: cell and z_step must be finite and > 0')
+    fr = Fraction(cell / z_step).limit_denominator(int(max_den))
+    a, b = fr.numerator, fr.denominator
+    if a < 1:
+        raise ValueError(f'voxel_metric: cell / z_step = {cell / z_step} is below 1 / (2 max_den): raise max_den')
+    w_xy, w_z = a * a, b * b
+    if px is not None and nz is not None:
+        far = w_xy * 2 * (int(px) - 1) ** 2 + w_z * (int(nz) - 1) ** 2
+        if far > 2 ** 31 - 2:
+            raise ValueError(f'voxel_metric: weights ({w_xy}, {w_z}) give a largest distance of {far} on a {px} x {px} x {nz} '
+                             f'grid, above the bound 2^31 - 2 = {2 ** 31 - 2}: lower max_den')
+    return w_xy, w_z, cell / a
+
+
 # ----------------------------------------------------------------------------------------------
 #  trajectories
 # ----------------------------------------------------------------------------------------------

@@ -426,8 +426,28 @@ class SemanticPointCloudAccumulator:
         (, 'visible'), 'input_occ', the pooled levels 'labels', 'state' (, 'visible'); 'packed': {s: payloads}, level 1 =
         'label', 'invalid' (, 'occluded'), 'bin', the pooled levels 'label' and 'invalid'.  label_map: 32 file values, None:
         label + 1 (0 is 'empty' in the files).  pca_amd.ssc.write_ssc_sample writes the files.
+        voxel_ssc_sample_filled is the same sample with the pinholes of accumulated lidar closed first.
         Nothing is written to the store."""
-        from bev_generator.bev_generator import DeviceWindow
+        return self._voxel_ssc_sample(present_idx, None, part, z_range, nz, classes, include_dyn, origins, cameras, stride,
+                                      max_depth, scales, input_frames, label_map, occluded)
+
+    def voxel_ssc_sample_filled(self, present_idx, fill_dist, **sample):
+        """Extension (no reference counterpart): voxel_ssc_sample(present_idx, **sample) with the pinholes of accumulated lidar
+        closed.  Far road and wall surfaces are hit in every second or third voxel only, and the voxels between the hits are
+        unseen -- a beam ends on a surface -- so they would land in .invalid.  fill_dist: a radius in metres; an unseen empty
+        voxel within it of a labelled one takes that voxel's label, of equally near ones the label of the smallest place
+        (SemBEVGenerator.voxel_distance_device, metric='metres'; a voxel a beam crossed stays free), and 'levels' and
+        'packed' are made from these 'filled' labels instead of 'labels': a filled voxel is occupied, so it leaves .invalid
+        by the pool's and the pack's own rule.  Returns voxel_ssc_sample's dict -- 'labels' is what it was -- plus 'filled'
+        uint8, 'dist2' and 'nearest' int32 [nz, px, px].  fill_dist=None is voxel_ssc_sample itself.
+        Nothing is written to the store."""
+        import inspect
+        bound = inspect.signature(self.voxel_ssc_sample).bind(present_idx, **sample)
+        bound.apply_defaults()
+        return self._voxel_ssc_sample(bound.arguments.pop('present_idx'), fill_dist, **bound.arguments)
+
+    def _voxel_ssc_sample(self, present_idx, fill_dist, part, z_range, nz, classes, include_dyn, origins, cameras, stride, max_depth,
+                          scales, input_frames, label_map, occluded):
         gen = self.sem_bev_generator
         if int(input_frames) < 1:
             raise ValueError('input_frames must be >= 1')
@@ -437,6 +457,22 @@ class SemanticPointCloudAccumulator:
         else:
             out = self.voxel_occupancy(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, include_dyn=include_dyn,
                                        origins=origins)
+        out['input_occ'], view = self._input_scan_occ(present_idx, z_range, nz, classes, include_dyn, input_frames)
+        labels = out['labels']
+        if fill_dist is not None:
+            d = gen.voxel_distance_device(labels, out['seen'], view, z_range, nz, metric='metres', max_dist=fill_dist,
+                                          fill_dist=fill_dist)
+            out.update({k: d[k] for k in ('filled', 'dist2', 'nearest')})
+            labels = d['filled']
+        out.update(gen.voxel_pyramid_device(labels, out['seen'], out.get('visible'), out['input_occ'], scales=scales,
+                                            label_map=label_map))
+        return out
+
+    def _input_scan_occ(self, present_idx, z_range, nz, classes, include_dyn, input_frames):
+        """('input_occ' uint8 [nz, px, px], view): 1 where a voxel_labels pass over the last input_frames frames of the
+        PRESENT part of the sample found a point -- the single-scan input of voxel_ssc_sample and voxel_distance."""
+        from bev_generator.bev_generator import DeviceWindow
+        gen = self.sem_bev_generator
         pc, rot_mat, view = self._unaugmented_part(present_idx, 'present')
         lo, hi = pc.frames()
         w = pc.window
@@ -444,9 +480,38 @@ class SemanticPointCloudAccumulator:
         # (keep_owed: the scan's window does not cover what the older frames owe, and this call writes nothing)
         one = gen.voxel_labels_device(scan, rot_mat, 0., 0., view, z_range, nz, classes=classes, include_dyn=include_dyn,
                                       keep_owed=True)
-        out['input_occ'] = (one['counts'] != 0).to(one['labels'].dtype)
-        out.update(gen.voxel_pyramid_device(out['labels'], out['seen'], out.get('visible'), out['input_occ'], scales=scales,
-                                            label_map=label_map))
+        return (one['counts'] != 0).to(one['labels'].dtype), view
+
+    def voxel_distance(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, include_dyn=False, origins=None,
+                       sites='labels', site_classes=None, input_frames=1, metric='metres', max_dist=None, fill_dist=None,
+                       fill_free=False, tsdf_trunc=None, flip=True):
+        """Extension (no reference counterpart): how far every voxel of voxel_occupancy's grid is from the nearest surface --
+        the exact distance transform of `part`'s volumes, on the device (SemBEVGenerator.voxel_distance_device, whose options
+        metric, max_dist, fill_dist, fill_free, tsdf_trunc and flip are passed on).  sites='labels': the distance is measured
+        from the labelled voxels of the part, those of site_classes (labels, as `classes` numbers them; None: all);
+        sites='input': from 'input_occ', the scan of the last input_frames frames that voxel_ssc_sample packs into .bin --
+        the TSDF input encoding of SSCNet-style models; 'nearest_label' and 'filled' then speak of that scan's single label
+        0.  Either way the sign of 'tsdf' and the voxels 'filled' may fill come from the part's own 'seen'.
+        Returns voxel_occupancy's dict, unchanged, plus 'dist2', 'nearest', 'nearest_label' (, 'filled', 'tsdf'), 'weights',
+        'unit' (, 'input_occ' with sites='input').  Nothing is written to the store."""
+        import torch
+        if sites not in ('labels', 'input'):
+            raise ValueError("sites must be 'labels' or 'input'")
+        gen = self.sem_bev_generator
+        out = self.voxel_occupancy(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, include_dyn=include_dyn,
+                                   origins=origins)
+        _, _, view = self._unaugmented_part(present_idx, part)
+        if sites == 'input':
+            if int(input_frames) < 1:
+                raise ValueError('input_frames must be >= 1')
+            out['input_occ'], _ = self._input_scan_occ(present_idx, z_range, nz, classes, include_dyn, input_frames)
+            # (the scan as a label volume: 0 where it found a point, 255 elsewhere)
+            source, site_classes = torch.where(out['input_occ'] != 0, 0, 255).to(torch.uint8), None
+        else:
+            source = out['labels']
+        out.update(gen.voxel_distance_device(source, out['seen'], view, z_range, nz, sites=site_classes, metric=metric,
+                                             max_dist=max_dist, fill_dist=fill_dist, fill_free=fill_free, tsdf_trunc=tsdf_trunc,
+                                             flip=flip))
         return out
 
     def carve_dynamic(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, end_margin=1, min_cross=2,
