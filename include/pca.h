@@ -602,8 +602,8 @@ int pca_bev_voxel_carve(pca_ctx *ctx, const pca_store *store, const int64_t *fra
  *       stats i64 [6]: kept points, foreground voxels, components, surviving components (n), kept points with ids >= 0,
  *         voxels of the largest surviving component.
  *       All sums are integer sums and all extremes integer extremes: exact and free of any order.
- *     Scope: the boxes are VOXEL boxes; a metric box tighter than the voxels is not computed (pca_amd.host_logic.instance_boxes
- *       turns the voxel box into metres).  No automatic call from integrate().
+ *     Scope: the boxes are VOXEL boxes (pca_amd.host_logic.instance_boxes turns the voxel box into metres); the metric box
+ *       tighter than the voxels is pca_bev_instance_boxes', from this call's ids.  No automatic call from integrate().
  *     Of prm, origin, R (a rotation about z, checked), dx, dy, view, height_filter and px are read.
  *     Limits: 1 <= px <= 1024, 1 <= nz <= 32, 1 <= n_labels <= 32, connectivity 6 or 26, 1 <= max_instances <= 65536,
  *       max_points < 2^31, z_lo finite, z_step finite and > 0, dyn_mode 0..2, min_points >= 1, min_voxels >= 1, a workspace
@@ -631,6 +631,66 @@ int pca_bev_voxel_instances(pca_ctx *ctx, const pca_store *store, const int64_t 
                             uint32_t *label_counts /*dev [max_instances][n_labels] or NULL*/,
                             int64_t  *stats        /*dev [6] or NULL*/,
                             void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Oriented metric boxes around the window's instances: for every instance id, the rectangle around the instance's points in
+ *       each direction of a caller-given table, and the direction chosen by one of two criteria -- the search-based rectangle
+ *       fit commonly used for lidar L-shapes.  No reference counterpart.  What turns "these points form one object"
+ *       (pca_bev_voxel_instances) into a box tighter than the voxels: auto-labelled 3D boxes from accumulated lidar.
+ *     ids: dev i32, one per window point, in window order -- what pca_bev_voxel_instances writes for the same window, but
+ *       only an input here: any i32 array is legal.  A point TAKES PART iff it lies inside the window cut at max_points and
+ *       0 <= ids[p] < n_rows.  Nothing else is tested (class, dyn, crop and height were tested when ids was made).
+ *     cos_sin: HOST f64 [n_angles][2], (c, s) of direction t; the caller makes the table, so no libm of this library enters
+ *       the result (pca_amd.host_logic.fit_angles: numpy's cos and sin of t (pi / 2) / n_angles).
+ *     Coordinates, all f64 (the library is built with -ffp-contract=off: only the explicit fma fuses).  Owed re-transforms
+ *       are applied oldest first, then x = X - ox, y = Y - oy, ax = fma(r1, y, r0 x) + dx, ay = fma(r4, y, r3 x) + dy -- the
+ *       view test's own expressions: a point's box coordinates are the ones its cell came from -- and z = (Z - oz) + 0.0.
+ *       For direction t, every operation rounded on its own: e1 = (c ax + s ay) + 0.0, e2 = (c ay - s ax) + 0.0.
+ *     Per (id, t): lo1, hi1, lo2, hi2 = the extremes of e1 and e2 over the instance's points; zlo, zhi those of z; n the
+ *       point count; area_t = (hi1 - lo1) (hi2 - lo2); near_t = the number of the instance's points with
+ *       min(min(e1 - lo1, hi1 - e1), min(e2 - lo2, hi2 - e2)) <= edge_dist, computed iff criterion == 1 or `near` is asked
+ *       for.  (A comparison with a NaN is false: a NaN is never an extreme and never near; an area_t that is NaN ranks as
+ *       +inf in the choice.  ids made by pca_bev_voxel_instances name points with finite coordinates only.)
+ *     t*: criterion 0 -- the smallest area_t, of equal ones the smallest t; criterion 1 -- the largest near_t, of equal ones
+ *       the smaller area_t, then the smallest t (the integer form of the "closeness" criterion: it keeps an L seen from two
+ *       sides from being boxed diagonally).
+ *     Output (dev, any of them may be NULL, not all; each is fully written by the call itself, on the stream):
+ *       fit f64 [n_rows][8]: lo1, hi1, lo2, hi2 at t*, zlo, zhi, area_t*, (double)t*; a row without a point: seven NaNs, -1;
+ *       fit_n u32 [n_rows][2]: n and near_t* (0 where near was not computed);
+ *       extents f64 [n_rows][n_angles][4]: lo1, hi1, lo2, hi2; a row without a point: +inf, -inf, +inf, -inf;
+ *       near u32 [n_rows][n_angles];
+ *       stats i64 [4]: points that take part, points with ids >= n_rows (skipped, not an error), rows with at least one
+ *         point, points of the largest row.
+ *       Only extremes and integer sums occur: the result is a function of the SET of (id, coordinates) pairs, not of their
+ *       order or of any scheduling.
+ *     Scope: the boxes stand on the ground plane (no tilt); nothing is tracked across samples, no instance is merged or
+ *       split, the variance criterion is not offered (its float sums would depend on the order) and no KITTI label_2 /
+ *       NuScenes file is written.  No automatic call from integrate().
+ *     Of prm, origin, R (a rotation about z, checked), dx and dy are read.
+ *     Limits: 1 <= n_rows <= 65536, 1 <= n_angles <= 256, every table entry finite, criterion 0 or 1, edge_dist finite and
+ *       >= 0, max_points < 2^31, a workspace of pca_bev_instance_boxes_workspace_bytes(max_points, n_rows, n_angles) bytes
+ *       (-1 outside these limits).
+ *     The call enqueues a fixed number of launches whatever the data (the near kernel iff near_t is needed) and never waits
+ *     for the device; no kernel waits for another workgroup.  The store is never written: owed re-transforms are applied to
+ *     the points that are read and stay owed.  A K1 noted by pca_k1_defer runs on its own first; a bin range armed by
+ *     pca_bev_bin_range / pca_bev_view_hint is neither used nor cleared.  A window above max_points is cut there and raises
+ *     PCA_STATUS_STORE_OVERFLOW; a window without points gives empty rows and zero stats.  Every argument is checked before
+ *     anything is launched; -1 with pca_last_error set ("bev instance boxes: ..."), nothing written.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t pca_bev_instance_boxes_workspace_bytes(int64_t max_points, int n_rows, int n_angles);
+int pca_bev_instance_boxes(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/,
+                           int slot_begin, int slot_end, int64_t max_points,
+                           const pca_bev_params *prm,
+                           const int32_t *ids     /*dev [window points]*/, int n_rows,
+                           const double *cos_sin  /*host [n_angles][2]*/, int n_angles, int criterion, double edge_dist,
+                           const double *pending_Ts, const int *pending_slot_ends, int n_pending,
+                           void *workspace /*dev*/, int64_t workspace_bytes,
+                           double   *fit     /*dev [n_rows][8] or NULL*/,
+                           uint32_t *fit_n   /*dev [n_rows][2] or NULL*/,
+                           double   *extents /*dev [n_rows][n_angles][4] or NULL*/,
+                           uint32_t *near    /*dev [n_rows][n_angles] or NULL*/,
+                           int64_t  *stats   /*dev [4] or NULL*/,
+                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The window of the store rendered into a pinhole camera with a z-buffer: dense depth, colour and class targets for an
@@ -1159,9 +1219,14 @@ enum {
 enum {
     PCA_K_VOXEL_POOL = PCA_K_TOTAL, PCA_K_VOXEL_PACK, PCA_K_END
 };
-/* A fourth block (the third is closed as well): the two kernels of pca_voxel_distance.  The profiler's tables end here. */
+/* A fourth block (the third is closed as well): the two kernels of pca_voxel_distance. */
 enum {
     PCA_K_VOXEL_DIST_LINES = PCA_K_END, PCA_K_VOXEL_DIST_ROWS, PCA_K_LAST
+};
+/* A fifth block (the fourth is closed too): the seven kernels of pca_bev_instance_boxes.  The profiler's tables end here. */
+enum {
+    PCA_K_BEV_BOX_TABLE = PCA_K_LAST, PCA_K_BEV_BOX_COUNT, PCA_K_BEV_BOX_OFFSETS, PCA_K_BEV_BOX_SCATTER, PCA_K_BEV_BOX_EXTENTS, PCA_K_BEV_BOX_NEAR,
+    PCA_K_BEV_BOX_CHOOSE, PCA_K_ALL
 };
 int pca_profile_enable(pca_ctx *ctx, int on);
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);

@@ -503,6 +503,20 @@ class SemBEVGenerator(BEVGenerator):
         return st.bev_voxel_instances(prm, *grid, table, n_labels, min_points=min_points, connectivity=connectivity,
                                       min_voxels=min_voxels, max_instances=max_instances, dyn=dyn, **frames)
 
+    # ---- oriented metric boxes around those instances (extension: pca_bev_instance_boxes) ------------
+    def instance_boxes_device(self, pc, ids, n_rows, rot_mat, dx, dy, aug_view_size, n_angles=90, criterion='area', edge_dist=0.2,
+                              cos_sin=None, extents=False, near=False):
+        """The oriented boxes of the instances `ids` names in one point set, in the frame voxel_instances_device clusters in
+        (same pc, rot_mat, dx, dy and aug_view_size): DeviceStore.bev_instance_boxes' dict of cuda tensors 'fit', 'fit_n',
+        'boxes', 'stats' (, 'extents', 'near').  ids: voxel_instances_device's 'ids' for the same pc (a cuda int32 tensor, one
+        per point); n_rows: the rows of the result, that call's max_instances.  The directions searched are
+        host_logic.fit_angles(n_angles), a quarter turn in n_angles steps, or the caller's own cos_sin [n, 2]."""
+        from pca_amd.host_logic import fit_angles
+        table = fit_angles(n_angles) if cos_sin is None else cos_sin
+        st, prm, frames = self._one_set_pass(pc, 'inst', rot_mat, dx, dy, aug_view_size)
+        return st.bev_instance_boxes(prm, ids, n_rows, table, criterion=criterion, edge_dist=edge_dist, extents=extents, near=near,
+                                     **frames)
+
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the
         partition column).  Builds the minimum-z map of ALL the rows (no static partition, no height filter: the method

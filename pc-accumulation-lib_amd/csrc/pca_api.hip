@@ -264,13 +264,13 @@ int pca_profile_enable(pca_ctx *ctx, int on)
     if (!ctx) return -1;
     prof_fold(ctx);
     ctx->profiling = on < 0 ? 0 : (on > 2 ? 2 : on);
-    if (on) for (int k = 0; k < PCA_K_LAST; ++k) { ctx->prof_ms[k] = 0; ctx->prof_n[k] = 0; }
+    if (on) for (int k = 0; k < PCA_K_ALL; ++k) { ctx->prof_ms[k] = 0; ctx->prof_n[k] = 0; }
     return 0;
 }
 
 int pca_profile_read(pca_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kernel_id < 0 || kernel_id >= PCA_K_LAST) return -1;
+    if (!ctx || kernel_id < 0 || kernel_id >= PCA_K_ALL) return -1;
     prof_fold(ctx);
     if (total_ms) *total_ms = ctx->prof_ms[kernel_id];
     if (launches) *launches = ctx->prof_n[kernel_id];

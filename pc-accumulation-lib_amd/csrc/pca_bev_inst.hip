@@ -36,7 +36,7 @@
 // in the workgroup's LDS (InstSlots: a key claims its slot by compare-and-swap, a key that finds its slot taken goes to global
 // memory directly); the slots are flushed once, by the kernel's last lines.
 // All sums are integer sums and all extremes integer extremes: the result does not depend on any order.
-// Scope: the boxes are voxel boxes (a metric box tighter than the voxels is not computed); the tile-local LDS stage for the
+// Scope: the boxes are voxel boxes (the metric box tighter than the voxels: pca_bev_boxes.hip); the tile-local LDS stage for the
 // merge is not built (profiles/bev_voxel_instances.txt has the plain form's time).  The store is never written.
 #include "pca_bev_voxel.h"
 #include "pca_point_pass.h"
@@ -85,39 +85,7 @@ __device__ __forceinline__ void inst_unite(int32_t *parent, int32_t a, int32_t b
         a = old;                                            // somebody linked a first: unite what it wrote with b
     }
 }
-// Every lane calls it with its key (0xffffffff: none).  f(key, lanes, leader) runs once per DISTINCT key of the wave, on all
-// lanes (it may reduce over the wave): `lanes` = the ballot of the lanes that hold the key, `leader` = this lane is their first.
-template <typename F>
-__device__ __forceinline__ void inst_for_each_key(uint32_t key, F f)
-{
-    unsigned long long todo = __ballot(key != 0xffffffffu);
-    while (todo) {                                          // (bounded by the wave's distinct keys, 64 at most)
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)key, leader);
-        const unsigned long long same = __ballot(key == kk);
-        f(kk, same, (int)(threadIdx.x & 63) == leader);
-        todo &= ~same;
-    }
-}
-// A workgroup's direct-mapped LDS cache in front of the global atomics on a few hot rows: a key claims its slot by
-// compare-and-swap; a key whose slot another key holds goes to global memory directly (claim returns -1).  The sums (val[0]) or
-// the six extremes (min, max, min, max, min, max) of a slot are flushed by the kernel's last lines, one global atomic each.
-#define INST_SLOTS 64
-struct InstSlots { uint32_t key[INST_SLOTS]; uint32_t val[INST_SLOTS][6]; };
-__device__ __forceinline__ void inst_slots_init(InstSlots &s, bool extremes)
-{
-    if (threadIdx.x < INST_SLOTS) {
-        s.key[threadIdx.x] = 0xffffffffu;
-        for (int j = 0; j < 6; ++j) s.val[threadIdx.x][j] = extremes && !(j & 1) ? 0xffffffffu : 0u;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ int inst_slots_claim(InstSlots &s, uint32_t key)
-{
-    const int slot = (int)((key * 2654435761u) >> 26);
-    const uint32_t old = atomicCAS(&s.key[slot], 0xffffffffu, key);
-    return old == 0xffffffffu || old == key ? slot : -1;
-}
+// (inst_for_each_key and InstSlots, the wave and workgroup aggregation in front of the hot rows: pca_point_pass.h)
 
 __global__ __launch_bounds__(INST_THREADS) void bev_inst_init(const InstArgs a)
 {

@@ -114,8 +114,8 @@ struct pca_ctx {
     int profiling = 0;                // 0 off, 1 every kernel launch, 2 whole units only (pca_profile_enable)
     std::vector<Ev> evs;              // recorded pairs not yet folded into the totals
     std::vector<Ev> free_evs;         // recycled events
-    double prof_ms[PCA_K_LAST] = {0};
-    int64_t prof_n[PCA_K_LAST] = {0};
+    double prof_ms[PCA_K_ALL] = {0};
+    int64_t prof_n[PCA_K_ALL] = {0};
 };
 
 // Launch wrapper: plain launch, or bracketed by events while profiling is on.

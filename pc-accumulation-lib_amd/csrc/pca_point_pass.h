@@ -1,5 +1,5 @@
 // pca_point_pass.h -- what the read-only passes that visit the window one stored point per thread share (bev_voxel_rays; bev_carve_ends,
-// bev_carve_rays, bev_carve_flags; render_zbuffer, render_resolve; bev_inst_points), as pca_bev_side.h is what the tiled passes
+// bev_carve_rays, bev_carve_flags; render_zbuffer, render_resolve; bev_inst_points; bev_box_count, bev_box_scatter), as pca_bev_side.h is what the tiled passes
 // share: the window and its cuts, the slot of a point, the counters' way to memory and the host's launch size.  The ONE copy of
 // each; the next pass of this family starts here.  Args: any argument block with st, frame_off, slot_begin, slot_end and
 // max_points (RayArgs, CarveArgs, RenderArgs; InstArgs hands in its v.s) -- no common base: every block keeps its own offsets.
@@ -65,6 +65,41 @@ __device__ __forceinline__ void point_count(unsigned long long *dst, U... n)
     }
     __syncthreads();
     if (tid < N && dst && s_sum[tid]) atomicAdd(dst + tid, s_sum[tid]);
+}
+
+// ---- aggregation in front of a few hot keys (bev_inst_compress, bev_inst_write, bev_inst_points; bev_box_count, bev_box_scatter) ----
+// Every lane calls it with its key (0xffffffff: none).  f(key, lanes, leader) runs once per DISTINCT key of the wave, on all
+// lanes (it may reduce over the wave): `lanes` = the ballot of the lanes that hold the key, `leader` = this lane is their first.
+template <typename F>
+__device__ __forceinline__ void inst_for_each_key(uint32_t key, F f)
+{
+    unsigned long long todo = __ballot(key != 0xffffffffu);
+    while (todo) {                                          // (bounded by the wave's distinct keys, 64 at most)
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)key, leader);
+        const unsigned long long same = __ballot(key == kk);
+        f(kk, same, (int)(threadIdx.x & 63) == leader);
+        todo &= ~same;
+    }
+}
+// A workgroup's direct-mapped LDS cache in front of the global atomics on a few hot rows: a key claims its slot by
+// compare-and-swap; a key whose slot another key holds goes to global memory directly (claim returns -1).  The sums (val[0]) or
+// the six extremes (min, max, min, max, min, max) of a slot are flushed by the kernel's last lines, one global atomic each.
+#define INST_SLOTS 64
+struct InstSlots { uint32_t key[INST_SLOTS]; uint32_t val[INST_SLOTS][6]; };
+__device__ __forceinline__ void inst_slots_init(InstSlots &s, bool extremes)
+{
+    if (threadIdx.x < INST_SLOTS) {
+        s.key[threadIdx.x] = 0xffffffffu;
+        for (int j = 0; j < 6; ++j) s.val[threadIdx.x][j] = extremes && !(j & 1) ? 0xffffffffu : 0u;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ int inst_slots_claim(InstSlots &s, uint32_t key)
+{
+    const int slot = (int)((key * 2654435761u) >> 26);
+    const uint32_t old = atomicCAS(&s.key[slot], 0xffffffffu, key);
+    return old == 0xffffffffu || old == key ? slot : -1;
 }
 
 // ---- host side ----

@@ -23,7 +23,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
            'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
-           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_voxel_distance_workspace_bytes', 'pca_voxel_distance', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
+           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_bev_instance_boxes_workspace_bytes', 'pca_bev_instance_boxes', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_voxel_distance_workspace_bytes', 'pca_voxel_distance', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
            'pca_host_track_poses', 'pca_host_track_segments', 'pca_host_track_set', 'pca_host_track_transform',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
@@ -44,7 +44,10 @@ KERNEL_IDS_INST = ('bev_inst_init', 'bev_inst_merge', 'bev_inst_compress', 'bev_
 KERNEL_IDS_CAMERA = ('bev_camera_rays', )                      # ... and the one of pca_bev_voxel_camera
 KERNEL_IDS_SSC = ('voxel_pool', 'voxel_pack')                  # ... and, in the third block, pca_voxel_pool's and pca_voxel_pack's
 KERNEL_IDS_DIST = ('voxel_dist_lines', 'voxel_dist_rows')      # ... and, in the fourth block, the two of pca_voxel_distance
+KERNEL_IDS_BOX = ('bev_box_table', 'bev_box_count', 'bev_box_offsets', 'bev_box_scatter', 'bev_box_extents', 'bev_box_near',
+                  'bev_box_choose')                        # ... and, in the fifth block, the seven of pca_bev_instance_boxes
 BEV_INST_COLS = 9
+BOX_CRITERIA = {'area': 0, 'edge': 1}
 DYN_MODES = {'static': 0, 'all': 1, 'dynamic': 2}
 BEV_EXTRA_PLANES = ('elevation_max', 'elevation_mean', 'intensity_mean')
 
@@ -260,6 +263,10 @@ def load():
     lib.pca_bev_voxel_instances.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, i64, C.POINTER(PcaBevParams), C.c_double,
                                             C.c_double, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i64,
                                             vp, vp, vp, vp, vp, vp]
+    lib.pca_bev_instance_boxes_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.pca_bev_instance_boxes_workspace_bytes.restype = i64
+    lib.pca_bev_instance_boxes.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, i64, C.POINTER(PcaBevParams), vp, i32, vp, i32,
+                                           i32, C.c_double, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.pca_render_camera.argtypes = [vp, C.POINTER(PcaStore), vp, i32, i32, i64, C.POINTER(PcaCamera), C.POINTER(PcaClassGroup),
                                       vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.pca_bev_voxel_camera.argtypes = [vp, C.POINTER(PcaBevParams), C.c_double, C.c_double, i32, vp, C.POINTER(PcaRayCamera),
@@ -427,7 +434,7 @@ class Context:
     def profile_read(self):
         """{kernel name: (total_ms, launches)} since profiling was enabled (synchronises)."""
         out = {}
-        for k, name in enumerate(KERNEL_IDS + KERNEL_IDS_VOXEL + KERNEL_IDS_RAYS + KERNEL_IDS_RENDER + KERNEL_IDS_CARVE + KERNEL_IDS_INST + KERNEL_IDS_CAMERA + KERNEL_IDS_SSC + KERNEL_IDS_DIST):
+        for k, name in enumerate(KERNEL_IDS + KERNEL_IDS_VOXEL + KERNEL_IDS_RAYS + KERNEL_IDS_RENDER + KERNEL_IDS_CARVE + KERNEL_IDS_INST + KERNEL_IDS_CAMERA + KERNEL_IDS_SSC + KERNEL_IDS_DIST + KERNEL_IDS_BOX):
             ms, n = C.c_double(0), C.c_int64(0)
             self.check(self.lib.pca_profile_read(self.h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)

@@ -9,6 +9,7 @@ Slots: frame k of the live window occupies slot ``head + k``; eviction advances 
 capacity run out the live window is moved to the front (rare, amortised).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -856,6 +857,81 @@ class DeviceStore:
         # the first maximum is the smallest label of a tie
         top_label = torch.where(label_counts.sum(dim=1) > 0, label_counts.argmax(dim=1), 255).to(torch.uint8)
         return {'inst': inst, 'ids': ids, 'table': table, 'label_counts': label_counts, 'top_label': top_label, 'stats': stats}
+
+    def bev_instance_boxes(self, prm, ids, n_rows, cos_sin, criterion='area', edge_dist=0.2, extents=False, near=False,
+                           first_frame=0, last_frame=None, max_points=None):
+        """Oriented metric boxes around the instances of the live frames [first_frame, last_frame) (pca_bev_instance_boxes).
+        ids: a cuda int32 tensor, one per point of the window in store order -- bev_voxel_instances' 'ids' for the same window
+        and the same `prm`, or any other grouping: a point takes part iff 0 <= ids[p] < n_rows.  cos_sin: f64 [n_angles, 2],
+        the directions to search (host_logic.fit_angles).  Per row and direction the rectangle around the row's points is
+        taken in the view frame of `prm` (of which origin, R, dx and dy are read); criterion 'area' chooses the direction of
+        the smallest rectangle, 'edge' the one with the most points within edge_dist metres of the rectangle's sides (of
+        equal counts the smaller rectangle) -- ties go to the first direction of the table.
+        Returns a dict of cuda tensors: 'fit' float64 [n_rows, 8] = lo1, hi1, lo2, hi2 along the chosen direction and across
+        it, z lo, z hi, the rectangle's area, the direction's index (seven NaNs and -1 for a row without a point); 'fit_n'
+        int32 [n_rows, 2] holding the u32 point count and the near count of the chosen direction (0 unless 'edge' or
+        near=True); 'boxes' float64 [n_rows, 7] = cx, cy, cz, length, width, height, yaw in the view frame (length >= width,
+        yaw in [0, pi); NaN for a row without a point; host_logic.oriented_boxes is its host form and adds the corners);
+        'stats' int64 [4]: points that take part, points with ids >= n_rows (skipped), rows with a point, points of the
+        largest row; extents=True: 'extents' float64 [n_rows, n_angles, 4]; near=True: 'near' int32 [n_rows, n_angles].
+        Only extremes and integer counts are taken: the same points in any order give the same bits.  (The length of `ids` is
+        checked against the window: one offset is read back, the call synchronises -- or, while a K1 is still noted, against
+        the window's upper bound, without a read.)
+        The store is not written: owed re-transforms are applied to what the call reads and stay owed.
+        max_points: the bound at which the window is cut (default: the live window's own bound)."""
+        lib = self.ctx.lib
+        if criterion not in _lib.BOX_CRITERIA:
+            raise ValueError("criterion must be 'area' or 'edge'")
+        table = np.ascontiguousarray(cos_sin, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError('cos_sin must be [n_angles, 2]')
+        n_rows, n_angles = int(n_rows), int(table.shape[0])
+        if not -(1 << 31) <= n_rows < 1 << 31:
+            raise ValueError('n_rows must fit 32 bits')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and ids.is_cuda and ids.dim() == 1 and ids.is_contiguous()):
+            raise ValueError('ids must be a contiguous 1-d cuda int32 tensor')
+        rows, angles = min(max(n_rows, 1), 65536), min(max(n_angles, 1), 256)     # (values outside are refused by the call)
+        last_frame, max_points, call = self._window_pass(
+            prm, first_frame, last_frame, max_points,
+            side=('boxes', lambda m, px: lib.pca_bev_instance_boxes_workspace_bytes(m, rows, angles)))
+        if self._k1_noted is not None:                     # (the newest frame's length is not known before its K1 has run)
+            lo, hi = 0, self.max_window_points()
+        else:
+            lo, hi = self.frame_off[[self.head + first_frame, self.head + last_frame]].tolist()
+        if ids.numel() < min(hi - lo, max_points):
+            raise ValueError('ids must hold one entry per point of the window')
+        if ids.numel() == 0:
+            ids = torch.zeros(1, dtype=torch.int32, device=self.device)           # (never read)
+        fit = torch.empty((rows, 8), dtype=torch.float64, device=self.device)
+        fit_n = torch.empty((rows, 2), dtype=torch.int32, device=self.device)
+        ext = torch.empty((rows, angles, 4), dtype=torch.float64, device=self.device) if extents else None
+        nr = torch.empty((rows, angles), dtype=torch.int32, device=self.device) if near else None
+        stats = torch.empty(4, dtype=torch.int64, device=self.device)
+        call(lib.pca_bev_instance_boxes, (ids.data_ptr(), n_rows, table.ctypes.data, n_angles, _lib.BOX_CRITERIA[criterion],
+                                          float(edge_dist)), (fit, fit_n, ext, nr, stats))
+        out = {'fit': fit, 'fit_n': fit_n, 'boxes': self._boxes_of(fit, table), 'stats': stats}
+        if extents:
+            out['extents'] = ext
+        if near:
+            out['near'] = nr
+        return out
+
+    def _boxes_of(self, fit, table):
+        """host_logic.oriented_boxes' boxes on the device: a few torch ops on `fit` and the uploaded table (cos, sin, atan2)."""
+        tab = torch.from_numpy(np.concatenate([table, np.arctan2(table[:, 1], table[:, 0])[:, None]], axis=1)).to(self.device)
+        t = fit[:, 7].to(torch.int64)
+        ok = t >= 0
+        row = tab[torch.where(ok, t, 0)]
+        nan = torch.full_like(fit[:, 0], float('nan'))
+        c, s, theta = (torch.where(ok, row[:, k], nan) for k in range(3))
+        lo1, hi1, lo2, hi2, zlo, zhi = (fit[:, k] for k in range(6))
+        m1, m2 = 0.5 * (lo1 + hi1), 0.5 * (lo2 + hi2)
+        d1, d2 = hi1 - lo1, hi2 - lo2
+        swap = d2 > d1
+        yaw = torch.remainder(torch.where(swap, theta + 0.5 * math.pi, theta), math.pi)
+        yaw = torch.where(yaw >= math.pi, torch.zeros_like(yaw), yaw)
+        return torch.stack([c * m1 - s * m2, s * m1 + c * m2, 0.5 * (zlo + zhi), torch.where(swap, d2, d1),
+                            torch.where(swap, d1, d2), zhi - zlo, yaw], dim=1)
 
     def render_camera(self, cam, first_frame=0, last_frame=None, classes=None, max_points=None):
         """The stored points of the live frames [first_frame, last_frame) rendered into a pinhole camera with a z-buffer

@@ -410,7 +410,8 @@ def instance_boxes(table, n, view, px, z_lo, z_step):
     row_min, row_max, k_min, k_max) in metres of the view frame: f64 [n, 6] as lo x, hi x, lo y, hi y, lo z, hi z.  A box
     spans whole voxels: cell i covers [(i - px / 2) view / px, (i + 1 - px / 2) view / px) and bin k covers
     [z_lo + k z_step, z_lo + (k + 1) z_step).  Columns are i; rows are image rows, row = px - 1 - j, so the smallest y
-    belongs to the LARGEST row.  (A metric box tighter than the voxels is not computed anywhere.)"""
+    belongs to the LARGEST row.  (The metric box tighter than the voxels, turned to the object's own direction, is
+    DeviceStore.bev_instance_boxes' and oriented_boxes below; it lies inside this one.)"""
     t = np.asarray(table).reshape(-1, 9)[:int(n)].astype(np.int64) & 0xffffffff    # (int32 that holds u32)
     cell = float(view) / px
     half = 0.5 * px
@@ -422,6 +423,43 @@ def instance_boxes(table, n, view, px, z_lo, z_step):
     out[:, 4] = z_lo + t[:, 7] * float(z_step)
     out[:, 5] = z_lo + (t[:, 8] + 1) * float(z_step)
     return out
+
+
+def fit_angles(n_angles):
+    """The table of directions DeviceStore.bev_instance_boxes searches by default: f64 [n_angles, 2] = (cos, sin) of
+    theta_t = t (pi / 2) / n_angles, numpy's own cos and sin.  A quarter turn is all a rectangle needs: the other three
+    quarters give the same rectangles with their sides renamed."""
+    n_angles = int(n_angles)
+    if n_angles < 1:
+        raise ValueError('fit_angles: n_angles must be >= 1')
+    theta = np.arange(n_angles, dtype=np.float64) * (0.5 * np.pi) / n_angles
+    return np.ascontiguousarray(np.stack([np.cos(theta), np.sin(theta)], axis=1))
+
+
+def oriented_boxes(fit, cos_sin):
+    """The rows of pca_bev_instance_boxes' `fit` (lo1, hi1, lo2, hi2, zlo, zhi, area, t) as boxes in the view frame: (boxes f64
+    [n, 7] = cx, cy, cz, length, width, height, yaw; corners f64 [n, 4, 2], the footprint, counter-clockwise from (lo1, lo2)).
+    The centre is the middle of the extents turned back, cx = c m1 - s m2, cy = s m1 + c m2; length >= width: where the e2
+    extent is the larger the two swap and yaw gains pi / 2; yaw = atan2(s, c) of the chosen direction, folded into [0, pi).
+    A row without a point (t = -1) is NaN throughout."""
+    fit = np.asarray(fit, dtype=np.float64).reshape(-1, 8)
+    cs = np.asarray(cos_sin, dtype=np.float64).reshape(-1, 2)
+    t = fit[:, 7].astype(np.int64)
+    ok = t >= 0
+    c = np.where(ok, cs[np.where(ok, t, 0), 0], np.nan)
+    s = np.where(ok, cs[np.where(ok, t, 0), 1], np.nan)
+    lo1, hi1, lo2, hi2, zlo, zhi = (fit[:, k] for k in range(6))
+    m1, m2 = 0.5 * (lo1 + hi1), 0.5 * (lo2 + hi2)
+    d1, d2 = hi1 - lo1, hi2 - lo2
+    swap = d2 > d1
+    yaw = np.mod(np.arctan2(s, c) + np.where(swap, 0.5 * np.pi, 0.), np.pi)
+    yaw = np.where(yaw >= np.pi, 0., yaw)                       # (a fold that rounds up to pi itself)
+    boxes = np.stack([c * m1 - s * m2, s * m1 + c * m2, 0.5 * (zlo + zhi), np.where(swap, d2, d1), np.where(swap, d1, d2),
+                      zhi - zlo, yaw], axis=1)
+    e1 = np.stack([lo1, hi1, hi1, lo1], axis=1)
+    e2 = np.stack([lo2, lo2, hi2, hi2], axis=1)
+    corners = np.stack([c[:, None] * e1 - s[:, None] * e2, s[:, None] * e1 + c[:, None] * e2], axis=2)
+    return boxes, corners
 
 
 def voxel_metric(cell, z_step, max_den=64, px=None, nz=None):

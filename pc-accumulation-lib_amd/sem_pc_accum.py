@@ -560,6 +560,34 @@ class SemanticPointCloudAccumulator:
                                                              min_points=min_points, connectivity=connectivity,
                                                              min_voxels=min_voxels, max_instances=max_instances, dyn=dyn)
 
+    def instance_boxes(self, present_idx, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, min_points=1, connectivity=26,
+                       min_voxels=1, max_instances=4096, dyn='static', n_angles=90, criterion='area', edge_dist=0.2, instances=None):
+        """Extension (no reference counterpart): an oriented metric box around every instance of voxel_instances -- the box a
+        detector is trained on or an object is tracked by, where the voxel box of a car parked at 30 degrees to the view is
+        about twice its footprint.  Runs voxel_instances with the arguments up to dyn (or takes its dict as `instances`, made
+        for the same present_idx and part), then, on the device, searches n_angles directions of a quarter turn for the
+        rectangle around each instance's points: criterion 'area' takes the smallest rectangle, 'edge' the one with the most
+        points within edge_dist metres of its sides (the search-based fit commonly used for lidar L-shapes: it keeps an L
+        seen from two sides from being boxed diagonally).  Only extremes and integer counts are taken, so the same points in
+        any order give the same bits.  n_angles=90 (one degree), criterion='area' and edge_dist=0.2 are this project's
+        choices, checked on synthetic scenes only (tests/test_instance_boxes_model.py); no real-data number exists.
+        Returns voxel_instances' dict plus 'fit' float64 [max_instances, 8], 'fit_n' int32 [max_instances, 2], 'boxes'
+        float64 [max_instances, 7] = cx, cy, cz, length, width, height, yaw (length >= width, yaw in [0, pi); NaN rows from
+        the number of instances on) and 'box_stats' int64 [4] (DeviceStore.bev_instance_boxes).  Boxes are in the sample's
+        un-augmented view frame, the frame of pca_amd.host_logic.instance_boxes, whose voxel box holds each of them.
+        Out of scope: boxes tilted out of the ground plane, tracking boxes across samples, merging or splitting instances,
+        the variance criterion (its float sums would depend on the order) and a KITTI label_2 / NuScenes writer.
+        Nothing is written to the store.  integrate() never calls this on its own."""
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        if instances is None:
+            instances = self.voxel_instances(present_idx, part=part, z_range=z_range, nz=nz, classes=classes, min_points=min_points,
+                                             connectivity=connectivity, min_voxels=min_voxels, max_instances=max_instances, dyn=dyn)
+        fit = self.sem_bev_generator.instance_boxes_device(pc, instances['ids'], int(instances['table'].shape[0]), rot_mat, 0., 0.,
+                                                           view, n_angles=n_angles, criterion=criterion, edge_dist=edge_dist)
+        out = dict(instances)
+        out.update(fit=fit['fit'], fit_n=fit['fit_n'], boxes=fit['boxes'], box_stats=fit['stats'])
+        return out
+
     def _render_defaults(self):
         """(P, (W, H)) of render_camera where the dataset has one camera the stored coordinates belong to; (None, None) here."""
         return None, None
