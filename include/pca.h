@@ -663,7 +663,7 @@ int pca_bev_voxel_instances(pca_ctx *ctx, const pca_store *store, const int64_t 
  *         point, points of the largest row.
  *       Only extremes and integer sums occur: the result is a function of the SET of (id, coordinates) pairs, not of their
  *       order or of any scheduling.
- *     Scope: the boxes stand on the ground plane (no tilt); nothing is tracked across samples, no instance is merged or
+ *     Scope: the boxes stand on the ground plane (no tilt); this call tracks nothing across samples (pca_voxel_instance_match gives the ids), no instance is merged or
  *       split, the variance criterion is not offered (its float sums would depend on the order) and no KITTI label_2 /
  *       NuScenes file is written.  No automatic call from integrate().
  *     Of prm, origin, R (a rotation about z, checked), dx and dy are read.
@@ -866,6 +866,65 @@ int pca_voxel_distance(pca_ctx *ctx, int px, int nz, const uint8_t *labels /*dev
                        double tsdf_unit, double tsdf_trunc, int tsdf_flip, void *workspace /*dev*/, int64_t workspace_bytes,
                        int32_t *dist2, int32_t *nearest, uint8_t *nearest_label, uint8_t *filled, float *tsdf /*each dev or NULL, not all*/,
                        void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The instances of one sample matched to those of the sample before it: stable ids over a sequence (pca_voxel_match.hip).
+ *       No reference counterpart.  Two instance volumes in this library's layout -- i32 [nz][px][px], -1 = no instance, what
+ *       pca_bev_voxel_instances writes as `inst`, though any i32 volume is legal -- and a map between their index spaces; the
+ *       call reads no store and no points.  Integer counts and maxima only, apart from the map itself.
+ *     Ids: a voxel of `cur` (`prev`) takes part iff 0 <= id < n_cur (n_prev); an id >= its row count or < -1 is skipped and
+ *       counted in stats[8] (stats[9]); it is not an error.
+ *     The map: M, HOST f64 [12], row-major 3 x 4, from the continuous index of a cur voxel centre to a continuous index in
+ *       prev (pca_amd.host_logic.voxel_index_map makes it from two grids and the rigid map between them).  Everything is f64,
+ *       every operation rounded on its own, no fma.  For a voxel (k, row, col) of cur with id b: u = col + 0.5, v = row + 0.5,
+ *       w = k + 0.5; q_i = ((M[i][0] u + M[i][1] v) + M[i][2] w) + M[i][3], i = 0, 1, 2: col', row', k'.  The image is IN VIEW
+ *       iff 0 <= q_0 < px && 0 <= q_1 < px && 0 <= q_2 < nz, tested on the f64 values before any conversion (a NaN is out of
+ *       view).  Then a = prev[floor q_2][floor q_1][floor q_0]; if 0 <= a < n_prev the pair (a, b) gains one.
+ *     C(a, b): the pair's count.  vox_cur[b]: the voxels of b in cur; in_view[b]: those whose image is in view; vox_prev[a]:
+ *       the voxels of a in prev.  best_prev(b): the a with the largest C(a, b) > 0, the smallest a among equal ones;
+ *       best_cur(a): the b with the largest C(a, b) > 0, the smallest b among equal ones.
+ *     b MATCHES a iff a = best_prev(b) && b = best_cur(a) && C >= min_overlap &&
+ *       (double)C >= min_iou * (double)(vox_prev[a] + vox_cur[b] - C) (one rounded product).
+ *     Tracks, t0 = *track_counter on entry: a matched b takes prev_track[a] (prev_track NULL: a itself); an unmatched b with
+ *       vox_cur[b] > 0 takes t0 + its rank among such b in ascending b; a row with vox_cur[b] = 0 takes -1 and uses up no
+ *       number; *track_counter leaves the call as t0 + the number of new tracks.  track_counter is read AND written on the
+ *       device, on the stream: calls chain without a host read.
+ *     Outputs, all dev, each may be NULL but not all, each fully written:
+ *       cur_track i32 [n_cur]; match i32 [n_cur]: the matched a or -1;
+ *       cur_info u32 [n_cur][4]: vox_cur, in_view, C at best_prev, best_prev + 1 (0: none);
+ *       prev_info u32 [n_prev][4]: vox_prev, C at best_cur, best_cur + 1, the matched b + 1;
+ *       track_vol i32 [nz][px][px]: cur_track of the voxel's id, -1 without a row;
+ *       track_ids i32 [n_ids]: cur_track of ids[p] (ids: dev i32 [n_ids], e.g. pca_bev_voxel_instances' per-point ids of cur),
+ *         -1 where the id is outside 0 .. n_cur - 1;
+ *       pairs u32 [cap_pairs][3]: a, b, C in NO defined order, unused rows 0xffffffff in all three words;
+ *       stats i64 [10]: cur voxels with a row, of which in view, sum of C, distinct pairs, dropped increments, matched, new
+ *         tracks, prev rows with vox_prev > 0 left unmatched (lost), cur voxels skipped, prev voxels skipped.
+ *     The pair table: open addressing over cap_pairs slots of the workspace with a BOUNDED probe; after cap_pairs probes an
+ *       increment is given up and counted in stats[4]; nothing spins, nothing waits.  With stats[4] > 0 only stats[0..1],
+ *       that stats[4] is > 0 (which increments were lost depends on the order of arrival), stats[8..9], vox_cur, in_view and
+ *       vox_prev are defined; the Python layers raise.
+ *     Every defined output but the order of `pairs` is a function of the two volumes and M alone: bests are 64-bit atomic
+ *       maxima of (C << 32 | ~id), counts are integer sums.
+ *     workspace: dev, pca_voxel_instance_match_workspace_bytes(n_prev, n_cur, cap_pairs) bytes (-1 outside the limits), 8-byte
+ *       aligned.
+ *     Limits: 1 <= px <= 1024, 1 <= nz <= 32; 1 <= n_prev, n_cur <= 65536; every entry of M finite; min_overlap >= 1; min_iou
+ *       finite, 0 .. 1; cap_pairs a power of two, 16 .. 2^22; prev, cur, M, track_counter not NULL; track_ids needs ids.
+ *     Every argument is checked before anything is launched; -1 with pca_last_error set ("voxel instance match: ..."), nothing
+ *       written.  Five launches whatever the volumes hold (four when neither track_vol nor track_ids is asked for); no wait on
+ *       the device or between workgroups.  PCA_VOXEL_MATCH_G = 1..2048 caps the workgroups; PCA_VOXEL_MATCH_FOLD=0 turns the
+ *       folding of equal keys within a wave off (same results).  The kernels carry no id of pca_profile_read.
+ *     min_overlap = 1 and min_iou = 0 are the shipped defaults of the Python layers: this project's choice, checked on
+ *       synthetic scenes only.
+ *     Out of scope: motion models or prediction, re-identifying a track after a sample in which it was unmatched, merging or
+ *     splitting instances, Hungarian or other globally optimal assignment, velocities, different px or nz between the samples.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t pca_voxel_instance_match_workspace_bytes(int n_prev, int n_cur, int cap_pairs);
+int pca_voxel_instance_match(pca_ctx *ctx, int px, int nz, const int32_t *prev /*dev*/, int n_prev, const int32_t *cur /*dev*/, int n_cur,
+                             const double *M /*host [12]*/, int min_overlap, double min_iou, int cap_pairs,
+                             const int32_t *prev_track /*dev [n_prev] or NULL*/, int32_t *track_counter /*dev [1], read and written*/,
+                             const int32_t *ids /*dev [n_ids] or NULL*/, int64_t n_ids, void *workspace /*dev*/, int64_t workspace_bytes,
+                             int32_t *cur_track, int32_t *match, uint32_t *cur_info, uint32_t *prev_info, int32_t *track_vol,
+                             int32_t *track_ids, uint32_t *pairs, int64_t *stats /*each dev or NULL, not all*/, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input normalisation of the semseg CNN on the device.  Replaces utils/onnx_utils.py:26-29, :35-36

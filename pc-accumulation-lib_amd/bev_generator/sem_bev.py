@@ -517,6 +517,26 @@ class SemBEVGenerator(BEVGenerator):
         return st.bev_instance_boxes(prm, ids, n_rows, table, criterion=criterion, edge_dist=edge_dist, extents=extents, near=near,
                                      **frames)
 
+    # ---- those instances matched to the previous sample's: stable ids (extension: pca_voxel_instance_match) ------------
+    def voxel_instance_match_device(self, prev, cur, T_cur_from_prev, prev_track=None, counter=None, min_overlap=1, min_iou=0.0,
+                                    cap_pairs=None, ids=None):
+        """The instances of the sample `cur` matched to those of the sample `prev`, each a record (inst, rows, geom): the
+        int32 [nz, px, px] instance volume voxel_instances_device returns as 'inst', the rows it is numbered over (that
+        call's max_instances) and geom = (origin xyz, R 3 x 3, dx, dy, view, px, z_lo, z_step), where its grid lies in the
+        store's coordinates at its moment (pca_amd.tracks.grid_geom).  T_cur_from_prev: f64 4 x 4, the rigid map the stored
+        points underwent between the two moments (store_frame() now times the inverse of store_frame() then).  The index
+        map is pca_amd.host_logic.voxel_index_map's; everything else is DeviceStore.voxel_instance_match's, whose dict of
+        cuda tensors is returned.  Two samples of different px or nz raise a ValueError: such grids are out of scope."""
+        from pca_amd import host_logic as hl
+        (prev_inst, n_prev, prev_geom), (cur_inst, n_cur, cur_geom) = prev, cur
+        if tuple(prev_inst.shape) != tuple(cur_inst.shape) or int(prev_geom[5]) != int(cur_geom[5]) or \
+                int(cur_geom[5]) != int(cur_inst.shape[1]):
+            raise ValueError('voxel_instance_match_device: the two samples must share px and nz')
+        M = hl.voxel_index_map(prev_geom, cur_geom, T_cur_from_prev)
+        return self._tmp_store('ssc').voxel_instance_match(prev_inst, n_prev, cur_inst, n_cur, M, prev_track=prev_track,
+                                                           counter=counter, min_overlap=min_overlap, min_iou=min_iou,
+                                                           cap_pairs=cap_pairs, ids=ids)
+
     def static_obj_partitioning_by_elev(self, pc: np.array, elev_thresh: float):
         """The reference's method (sem_bev.py:556-591).  pc: pre-gridded rows (columns 0, 1 = cell indices, 2 = z, 8 = the
         partition column).  Builds the minimum-z map of ALL the rows (no static partition, no height filter: the method

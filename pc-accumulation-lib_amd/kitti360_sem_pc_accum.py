@@ -314,6 +314,9 @@ class Kitti360SemanticPointCloudAccumulator(SemanticPointCloudAccumulator):
         self.store.append_kitti(frames, self.P_velo_frame, shape[0], shape[1], self.semseg_filters,
                                 sample_mode=self.sample_mode)
         self.store.retransform_batch(np.stack(Ts), len(frames))
+        for k, T_new_prev in enumerate(Ts):             # (as integrate(): the very first frame finds nothing stored to move)
+            if k > 0 or len(self._track) > 0:
+                self._note_store_motion(T_new_prev)
         removed, total = [], 0
         for T_new_prev in Ts:                           # host bookkeeping, frame by frame as integrate() does
             idx, path_length = self._track.step(T_new_prev, self.horizon_dist)

@@ -23,7 +23,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_nusc_sample_filter_transform', 'pca_nusc_sample_filter_transform_ex', 'pca_nusc_sample_filter_transform_batch', 'pca_sample_bilinear', 'pca_nusc_project_cams',
            'pca_nusc_merge_sweeps_workspace_bytes', 'pca_nusc_merge_sweeps', 'pca_retransform', 'pca_retransform_batch_tail',
            'pca_mark_dynamic',
-           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_bev_instance_boxes_workspace_bytes', 'pca_bev_instance_boxes', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_voxel_distance_workspace_bytes', 'pca_voxel_distance', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
+           'pca_bev_workspace_bytes', 'pca_bev_generate', 'pca_bev_generate_ex', 'pca_bev_generate_chain', 'pca_bev_generate_many', 'pca_bev_class_workspace_bytes', 'pca_bev_class_planes', 'pca_bev_elev_workspace_bytes', 'pca_bev_elev_partition', 'pca_bev_voxel_workspace_bytes', 'pca_bev_voxel_labels', 'pca_bev_voxel_rays', 'pca_bev_carve_workspace_bytes', 'pca_bev_voxel_carve', 'pca_bev_instances_workspace_bytes', 'pca_bev_voxel_instances', 'pca_bev_instance_boxes_workspace_bytes', 'pca_bev_instance_boxes', 'pca_render_camera', 'pca_bev_voxel_camera', 'pca_voxel_pool', 'pca_voxel_pack', 'pca_voxel_distance_workspace_bytes', 'pca_voxel_distance', 'pca_voxel_instance_match_workspace_bytes', 'pca_voxel_instance_match', 'pca_bev_warp', 'pca_lanes_workspace_bytes', 'pca_lanes_transform', 'pca_lanes_to_grid', 'pca_image_to_nchw_f32', 'pca_voxel_dedup_workspace_bytes', 'pca_voxel_dedup', 'pca_icp_workspace_bytes', 'pca_icp_register', 'pca_host_ego_to_grid',
            'pca_host_gemv4_probe', 'pca_host_gemv4_mode', 'pca_host_incr_probe', 'pca_host_incr_blocks', 'pca_host_track_create', 'pca_host_track_destroy', 'pca_host_track_len', 'pca_host_track_n_segments',
            'pca_host_track_poses', 'pca_host_track_segments', 'pca_host_track_set', 'pca_host_track_transform',
            'pca_host_track_append', 'pca_host_track_push_segment', 'pca_host_track_incr', 'pca_host_track_evict_beyond',
@@ -277,6 +277,11 @@ def load():
     lib.pca_voxel_distance_workspace_bytes.restype = i64
     lib.pca_voxel_distance.argtypes = [vp, i32, i32, vp, vp, C.POINTER(PcaClassGroup), i32, i32, i64, i64, i32, C.c_double, C.c_double,
                                        i32, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.pca_voxel_instance_match_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.pca_voxel_instance_match_workspace_bytes.restype = i64
+    # (M: host f64 [12]; prev_track, ids and every output may be NULL)
+    lib.pca_voxel_instance_match.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, i64, vp, i64,
+                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pca_bev_warp.argtypes = [vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.pca_voxel_dedup_workspace_bytes.restype = C.c_int64
     lib.pca_voxel_dedup_workspace_bytes.argtypes = [i64, i32]

@@ -60,6 +60,7 @@ class DeviceStore:
         self._render_keys = {}           # (H, W) -> the z-buffer's keys (render_camera)
         self._dedup_ws = None
         self._dist_ws = None              # pca_voxel_distance's scratch, grown to the largest volume seen
+        self._match_ws = None             # pca_voxel_instance_match's scratch, grown to the largest call seen
         self._obs_out = None
         self._k1_noted = None    # what the K1 noted by the last append_kitti_obs still reads (device tensors), or None
         self._pend_T = (C.c_double * (16 * self.CHAIN_MAX))()      # the owed chain as the C calls take it
@@ -1124,6 +1125,96 @@ class DeviceStore:
                                              float(trunc), 1 if flip else 0, ptr(ws), 0 if ws is None else ws.numel(),
                                              out['dist2'].data_ptr(), out['nearest'].data_ptr(), out['nearest_label'].data_ptr(),
                                              ptr(out.get('filled')), ptr(out.get('tsdf')), ctx.stream()))
+        return out
+
+    def _i32_volume(self, v, name, shape=None):
+        """An int32 [nz, px, px] volume on the device (numpy arrays are uploaded), checked against `shape`."""
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.array(v, dtype=np.int32))          # (a copy: the caller's array may be read-only)
+        v = v.to(device=self.device).contiguous()
+        if v.dtype != torch.int32 or v.dim() != 3 or v.shape[1] != v.shape[2] or (shape is not None and tuple(v.shape) != shape):
+            raise ValueError(f'{name} must be int32 [nz, px, px]' + ('' if shape is None else ', the shape of prev_inst'))
+        return v
+
+    def voxel_instance_match(self, prev_inst, n_prev, cur_inst, n_cur, index_map, prev_track=None, counter=None, min_overlap=1,
+                             min_iou=0.0, cap_pairs=None, ids=None):
+        """The instances of one sample matched to those of the sample before it (pca_voxel_instance_match): ids that hold over
+        a sequence.  prev_inst, cur_inst: int32 [nz, px, px] instance volumes of one shape, -1 = no instance (what
+        bev_voxel_instances returns as 'inst'; cuda tensors or numpy arrays, uploaded); n_prev, n_cur: their rows -- a voxel
+        whose id is not in [0, rows) takes no part and is counted.  index_map: f64 3 x 4, from the continuous index (col, row,
+        k) of a cur voxel centre to that in prev (host_logic.voxel_index_map).  C(a, b) counts the voxels of cur instance b
+        whose centre lands in prev instance a; b matches a iff each is the other's best partner (largest C, smallest id among
+        equal ones), C >= min_overlap and C >= min_iou (vox_prev[a] + vox_cur[b] - C).  prev_track: int32 [n_prev], the tracks
+        of prev's rows (None: a row is its own track); counter: a cuda int32 [1] tensor holding the next unused track number,
+        read and moved on ON THE DEVICE (None: a fresh one holding 0) -- pass both from call to call and a sequence chains.
+        ids: int32 per-point instance ids of cur (bev_voxel_instances' 'ids').
+        Returns a dict of cuda tensors: 'cur_track' int32 [n_cur] (the matched row's track, a new number for an unmatched row
+        with a voxel, -1 for a row without one); 'match' int32 [n_cur] (the prev row or -1); 'cur_info' int32 [n_cur, 4]
+        holding u32 vox_cur, in_view, C at the best prev row, that row + 1; 'prev_info' int32 [n_prev, 4]: vox_prev, C at the
+        best cur row, that row + 1, the matched row + 1; 'track_vol' int32 [nz, px, px]; 'track_ids' (with ids); 'pairs' int32
+        [n, 3] = a, b, C, compacted and sorted by (b, a) on the device; 'stats' int64 [10] (pca.h) and 'counter'.
+        cap_pairs: the slots of the pair table, a power of two (None: the next one >= 4 max(n_prev, n_cur)); if an increment
+        found no slot the call raises a RuntimeError -- stats is read back for that, the call synchronises.
+        min_overlap=1 and min_iou=0 are this project's choice, checked on synthetic scenes only.
+        Neither the store nor the owed re-transforms are read or written."""
+        prev_inst = self._i32_volume(prev_inst, 'prev_inst')
+        shape = tuple(prev_inst.shape)
+        cur_inst = self._i32_volume(cur_inst, 'cur_inst', shape)
+        nz, px = shape[0], shape[1]
+        n_prev, n_cur = int(n_prev), int(n_cur)
+        M = np.ascontiguousarray(index_map, dtype=np.float64)
+        if M.shape != (3, 4):
+            raise ValueError('index_map must be 3 x 4')
+        if cap_pairs is None:
+            cap_pairs = 16
+            while cap_pairs < 4 * max(n_prev, n_cur, 1) and cap_pairs < 1 << 22:
+                cap_pairs *= 2
+        cap_pairs = int(cap_pairs)
+
+        def i32_vector(t, name, n=None):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                t = torch.from_numpy(np.array(t, dtype=np.int32))
+            t = t.to(device=self.device).contiguous()
+            if t.dtype != torch.int32 or t.dim() != 1 or (n is not None and t.numel() != n):
+                raise ValueError(f'{name} must be int32 [{"n" if n is None else n}]')
+            return t
+        prev_track = i32_vector(prev_track, 'prev_track', max(n_prev, 0))
+        ids = i32_vector(ids, 'ids')
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if not (isinstance(counter, torch.Tensor) and counter.dtype == torch.int32 and counter.is_cuda and counter.numel() == 1):
+            raise ValueError('counter must be a cuda int32 tensor of one element')
+        ctx = self.ctx
+        need = int(ctx.lib.pca_voxel_instance_match_workspace_bytes(n_prev, n_cur, cap_pairs))
+        if need > 0 and (self._match_ws is None or self._match_ws.numel() < need):
+            self._match_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._match_ws
+        rows_c, rows_p = min(max(n_cur, 1), 65536), min(max(n_prev, 1), 65536)   # (values outside are refused by the call)
+        slots = cap_pairs if need > 0 else 1
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = {'cur_track': torch.empty(rows_c, **i32), 'match': torch.empty(rows_c, **i32),
+               'cur_info': torch.empty((rows_c, 4), **i32), 'prev_info': torch.empty((rows_p, 4), **i32),
+               'track_vol': torch.empty(shape, **i32)}
+        if ids is not None:
+            out['track_ids'] = torch.empty(ids.numel(), **i32)
+        pairs = torch.empty((slots, 3), **i32)
+        stats = torch.empty(10, dtype=torch.int64, device=self.device)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()       # noqa: E731
+        ctx.check(ctx.lib.pca_voxel_instance_match(
+            ctx.h, px, nz, prev_inst.data_ptr(), n_prev, cur_inst.data_ptr(), n_cur, M.ctypes.data, int(min_overlap), float(min_iou),
+            cap_pairs, ptr(prev_track), counter.data_ptr(), ptr(ids), 0 if ids is None else ids.numel(), ptr(ws),
+            0 if ws is None else ws.numel(), out['cur_track'].data_ptr(), out['match'].data_ptr(), out['cur_info'].data_ptr(),
+            out['prev_info'].data_ptr(), out['track_vol'].data_ptr(), ptr(out.get('track_ids')), pairs.data_ptr(), stats.data_ptr(),
+            ctx.stream()))
+        dropped = int(stats[4].item())                     # the one read-back
+        if dropped:
+            raise RuntimeError(f'pca: voxel instance match: {dropped} increments found no slot in the pair table of {cap_pairs} '
+                               f'(raise cap_pairs)')
+        used = pairs[pairs[:, 0] != -1]
+        order = torch.argsort(used[:, 1].to(torch.int64) * 65536 + used[:, 0].to(torch.int64))
+        out.update(pairs=used[order], stats=stats, counter=counter)
         return out
 
     def bev_many(self, jobs, out16):

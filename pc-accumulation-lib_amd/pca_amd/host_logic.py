@@ -425,6 +425,33 @@ def instance_boxes(table, n, view, px, z_lo, z_step):
     return out
 
 
+def voxel_index_to_store(geom):
+    """A, f64 4 x 4: the continuous index (u, v, w) = (col, row, k) of a voxel grid -> store coordinates, the inverse of the
+    view's cell rule that instance_boxes documents.  geom = (origin xyz, R 3 x 3 about z, dx, dy, view, px, z_lo, z_step):
+    cell i covers [(i - px / 2) view / px, ...), so a_x = (u - px / 2) view / px; the image row is px - 1 - j, so
+    a_y = (px / 2 - v) view / px; bin k covers [z_lo + k z_step, ...), so z = z_lo + w z_step above the origin; and the view
+    frame is a = R (p - origin) + (dx, dy), so p = origin + R^T (a - (dx, dy, 0))."""
+    origin, R, dx, dy, view, px, z_lo, z_step = geom
+    cell, half = float(view) / int(px), 0.5 * int(px)
+    S = np.array([[cell, 0., 0., -half * cell], [0., -cell, 0., half * cell], [0., 0., float(z_step), float(z_lo)], [0., 0., 0., 1.]])
+    back = np.eye(4)
+    back[:3, :3] = np.asarray(R, dtype=np.float64).reshape(3, 3).T
+    back[:3, 3] = np.asarray(origin, dtype=np.float64).reshape(3) - back[:3, :3] @ np.array([float(dx), float(dy), 0.])
+    return back @ S
+
+
+def voxel_index_map(prev_geom, cur_geom, T_cur_from_prev):
+    """M, f64 3 x 4, of DeviceStore.voxel_instance_match: the continuous index of a voxel centre of the CURRENT sample's grid ->
+    the continuous index of the same place in the PREVIOUS sample's grid, M = inv(A_prev) inv(T) A_cur with A =
+    voxel_index_to_store(geom) and T_cur_from_prev the rigid 4 x 4 the stored points underwent between the two samples
+    (p_cur = T p_prev: SemanticPointCloudAccumulator.store_frame() of the later moment times the inverse of the earlier
+    one's; the identity where the store keeps one frame for good, as NuScenes does).  numpy f64 throughout; a singular
+    matrix raises numpy's LinAlgError."""
+    T = np.asarray(T_cur_from_prev, dtype=np.float64).reshape(4, 4)
+    M = np.linalg.inv(voxel_index_to_store(prev_geom)) @ np.linalg.inv(T) @ voxel_index_to_store(cur_geom)
+    return np.ascontiguousarray(M[:3])
+
+
 def fit_angles(n_angles):
     """The table of directions DeviceStore.bev_instance_boxes searches by default: f64 [n_angles, 2] = (cos, sin) of
     theta_t = t (pi / 2) / n_angles, numpy's own cos and sin.  A quarter turn is all a rectangle needs: the other three

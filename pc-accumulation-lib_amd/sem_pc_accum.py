@@ -39,6 +39,8 @@ class SemanticPointCloudAccumulator:
         self.rgbs = []
         self.semsegs = []
         self._store = None               # created on first use (needs the GPU)
+        # the rigid map the stored points have undergone since construction (store_frame): bookkeeping only
+        self._store_frame = np.eye(4)
         self._store_args = {}
         # opt-in voxel de-duplication of the accumulation buffer (extension, off by default: the reference only
         # evicts whole frames).  Set the attribute, or PCA_VOXEL_DEDUP=<voxel size in m> [PCA_VOXEL_DEDUP_EVERY=<k>].
@@ -115,7 +117,20 @@ class SemanticPointCloudAccumulator:
     def update_sem_pcs(self, T_new_prev):
         """Every stored point p <- T_new_prev p, in place on the device (K2; deferred so that a BEV that
         follows immediately applies it in its first pass -- same roundings, one read of the store less)."""
-        self.store.retransform(np.asarray(T_new_prev, dtype=np.float64), defer=True)
+        T_new_prev = np.asarray(T_new_prev, dtype=np.float64)
+        self._note_store_motion(T_new_prev)
+        self.store.retransform(T_new_prev, defer=True)
+
+    def _note_store_motion(self, T_new_prev):
+        """The stored points are re-expressed by T_new_prev (p <- T_new_prev p): store_frame() follows."""
+        self._store_frame = np.asarray(T_new_prev, dtype=np.float64).reshape(4, 4) @ self._store_frame
+
+    def store_frame(self):
+        """Extension (no reference counterpart): the product, f64 4 x 4, of every rigid map the stored points have been
+        re-expressed by since construction, newest on the left (a copy; the identity for a class that never re-expresses its
+        store, as NuScenes).  Two moments' values give the map the stored points underwent between them: T_cur_from_prev =
+        F_cur inv(F_prev), what pca_amd.host_logic.voxel_index_map and track_instances need.  Bookkeeping only."""
+        return self._store_frame.copy()
 
     def remove_observations(self):
         """Appends the newest path segment and evicts frames beyond the memory horizon."""
@@ -575,7 +590,8 @@ class SemanticPointCloudAccumulator:
         float64 [max_instances, 7] = cx, cy, cz, length, width, height, yaw (length >= width, yaw in [0, pi); NaN rows from
         the number of instances on) and 'box_stats' int64 [4] (DeviceStore.bev_instance_boxes).  Boxes are in the sample's
         un-augmented view frame, the frame of pca_amd.host_logic.instance_boxes, whose voxel box holds each of them.
-        Out of scope: boxes tilted out of the ground plane, tracking boxes across samples, merging or splitting instances,
+        Out of scope: boxes tilted out of the ground plane, tracking boxes across samples (track_instances(boxes=True) gives
+        the instances ids that hold over a sequence and carries these boxes alongside), merging or splitting instances,
         the variance criterion (its float sums would depend on the order) and a KITTI label_2 / NuScenes writer.
         Nothing is written to the store.  integrate() never calls this on its own."""
         pc, rot_mat, view = self._unaugmented_part(present_idx, part)
@@ -586,6 +602,57 @@ class SemanticPointCloudAccumulator:
                                                            view, n_angles=n_angles, criterion=criterion, edge_dist=edge_dist)
         out = dict(instances)
         out.update(fit=fit['fit'], fit_n=fit['fit_n'], boxes=fit['boxes'], box_stats=fit['stats'])
+        return out
+
+    def track_instances(self, present_idx, state=None, part='full', z_range=(-2.0, 4.4), nz=32, classes=None, min_points=1,
+                        connectivity=26, min_voxels=1, max_instances=4096, dyn='static', min_overlap=1, min_iou=0.0, boxes=False,
+                        n_angles=90, criterion='area', edge_dist=0.2):
+        """Extension (no reference counterpart): instance ids that hold over a sequence of samples.  voxel_instances numbers a
+        sample's instances by their smallest voxel place, which says nothing about the next sample; this runs voxel_instances
+        with the arguments up to dyn (instance_boxes with boxes=True, which adds 'fit', 'fit_n', 'boxes' and 'box_stats') and
+        then, on the device, matches the sample's instance volume against the previous sample's, carried in `state`
+        (SemBEVGenerator.voxel_instance_match_device): the centre of every instance voxel is taken through the rigid map the
+        store underwent since then (store_frame()) into the previous grid; an instance continues the track of the previous
+        instance it overlaps most, if that one overlaps it most too and the overlap is at least min_overlap voxels and min_iou
+        of the union; every other instance opens a new track.  state=None starts a sequence: every instance is new, from 0.
+        Returns that dict plus 'track' int32 [max_instances] (per instance; -1 for a row without a voxel), 'track_vol' int32
+        [nz, px, px], 'track_ids' int32 (one per point of the part, as 'ids'), 'match' int32 [max_instances] (the previous
+        sample's row or -1), 'match_stats' int64 [10] (pca.h: pca_voxel_instance_match) and 'state', a pca_amd.tracks.TrackState
+        to pass to the next call.  The track counter lives on the device and no count is read back, except the one word that
+        says whether the pair table overflowed (a RuntimeError).
+        min_overlap=1 and min_iou=0 are this project's choice, checked on synthetic scenes only
+        (tests/test_voxel_tracks_model.py); no real-data number exists.
+        Out of scope: motion models or prediction, re-identifying a track after a sample in which it was unmatched, merging
+        or splitting instances (the larger overlap keeps the track, the rest are new), Hungarian or other globally optimal
+        assignment, velocities, different px or nz between samples (a ValueError).
+        Nothing is written to the store.  integrate() never calls this on its own."""
+        import torch
+
+        from pca_amd.tracks import TrackState, grid_geom
+        gen = self.sem_bev_generator
+        pc, rot_mat, view = self._unaugmented_part(present_idx, part)
+        args = dict(part=part, z_range=z_range, nz=nz, classes=classes, min_points=min_points, connectivity=connectivity,
+                    min_voxels=min_voxels, max_instances=max_instances, dyn=dyn)
+        if boxes:
+            out = dict(self.instance_boxes(present_idx, n_angles=n_angles, criterion=criterion, edge_dist=edge_dist, **args))
+        else:
+            out = dict(self.voxel_instances(present_idx, **args))
+        inst, rows = out['inst'], int(out['table'].shape[0])
+        z_lo, z_step, _ = gen._voxel_grid(z_range, nz)
+        geom = grid_geom(pc.window.origin, rot_mat, 0., 0., view, gen.pixel_size, z_lo, z_step)
+        frame = self.store_frame()
+        if state is None:
+            # (a sequence starts against a sample without instances: nothing matches, every instance is new)
+            prev = (torch.full_like(inst, -1), 1, geom)
+            prev_track, counter, T, samples = None, None, np.eye(4), 0
+        else:
+            prev, prev_track, counter, samples = state.record(), state.track, state.counter, state.samples
+            T = frame @ np.linalg.inv(state.frame)
+        m = gen.voxel_instance_match_device(prev, (inst, rows, geom), T, prev_track=prev_track, counter=counter,
+                                            min_overlap=min_overlap, min_iou=min_iou, ids=out['ids'])
+        out.update(track=m['cur_track'], track_vol=m['track_vol'], track_ids=m['track_ids'], match=m['match'],
+                   match_stats=m['stats'],
+                   state=TrackState(inst.clone(), rows, m['cur_track'], m['counter'], geom, frame, samples + 1))
         return out
 
     def _render_defaults(self):
