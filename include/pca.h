@@ -119,7 +119,7 @@ int pca_kitti_project_sample_filter_ex(pca_ctx *ctx, const pca_kitti_frame *fram
  *     stable compaction -> ego->world transform -> append.
  *     Replaces nuscenes_oracle_sem_pc_accum.py:457-501 and datasets/nuscenes_utils.py:181-214 ('nearest').
  *     pc: dev [n,7] f64 rows x,y,z,intensity,u,v,inst;  cam_idx: dev [n] int64 (-1: on no image);
- *     imgs: dev [ncam,H,W,3] u8; sems: dev [ncam,H,W] u8;  T: 4x4 row-major f64 (T_ego_world).
+ *     imgs: dev [ncam,H,W,3] u8; sems: dev [ncam,H,W] u8;  T: host, 4x4 row-major f64 (T_ego_world), not NULL.
  *     A point whose cam_idx lies outside [0, ncam) is dropped silently, whatever its u, v (the reference never looks at
  *     them).  A point assigned to a camera whose u, v do not satisfy 1 < u < W - 1, 1 < v < H - 1 (on a bound, outside, NaN,
  *     +-inf, -0.0) raises PCA_STATUS_UV_OUT_OF_IMAGE and is DROPPED: the call stores exactly the rows it would store without
@@ -170,7 +170,8 @@ int pca_sample_bilinear(pca_ctx *ctx, const double *map /*dev*/, int H, int W, c
  *     pc_lidar dev [n,3] f64.  T_cam_from_glob [ncam,16], K [ncam,9], wh [ncam,2] host arrays.
  *     Outputs dev: pc_in_ego [n,3], uv [n,2] f64, cam_idx [n] int64.
  *     ncam: 0 .. 8, anything else returns -1 and writes nothing; ncam = 0 writes pc_in_ego, uv = 0 and cam_idx = -1.
- *     n <= 0 returns 0 and writes nothing.  A point is taken by camera j where cz > 1e-3, 1 < u < w_j - 1 and
+ *     n <= 0 returns 0 and writes nothing.  With n > 0, pc_lidar, the two transforms and the three outputs must not be NULL,
+ *     nor T_cam_from_glob, K and wh with ncam > 0 (-1, nothing launched).  A point is taken by camera j where cz > 1e-3, 1 < u < w_j - 1 and
  *     1 < v < h_j - 1, all strict; a point no camera takes (NaN and inf coordinates among them) keeps uv = 0, cam_idx = -1.
  *     Every output is bit-equal to the reference's but for the sign of a NaN the arithmetic itself produced (0 x inf,
  *     inf - inf in pc_in_ego of a point with an infinite coordinate): gfx950 clears it, x86 sets it.  The same holds for the
@@ -227,7 +228,7 @@ int pca_nusc_merge_sweeps(pca_ctx *ctx, const float *raw /*dev*/, int64_t n_poin
  * K2  in-place rigid re-transform of every stored point of frames [slot_begin, slot_end).
  *     Replaces sem_pc_accum.py:167-183 (update_sem_pcs).  Ts: n_T 4x4 row-major matrices applied one
  *     after the other (n_T = 1 is the reference's per-step call; n_T > 1 applies a backlog of steps in
- *     one pass over HBM with identical roundings).
+ *     one pass over HBM per 16 transforms, with identical roundings).  0 <= n_T <= 65535 (more: -1, nothing launched).
  * ------------------------------------------------------------------------------------------------ */
 int pca_retransform(pca_ctx *ctx, const pca_store *store, const int64_t *frame_off /*dev*/, int slot_begin,
                     int slot_end, const double *Ts, int n_T, void *stream);
@@ -271,7 +272,10 @@ int pca_voxel_dedup(pca_ctx *ctx, const pca_store *store, int64_t *frame_off /*d
  *     correspondences min(max_corr_dist, 4 m)); sweeps must lie within +-128 m (x, y), -16..16 m (z) of the sensor.
  *     src_pts / tgt_pts: dev [n,4] f32 rows x,y,z,(ignored).  init / T_out: host 4x4 row-major; T_out maps source
  *     coordinates into the target frame (T_new_prev).  Synchronises `stream` before returning.
+ *     max_iter < 1 means 30; max_iter above PCA_ICP_MAX_ITER is refused before anything is launched ("icp: max_iter must not
+ *     exceed 32766").  A registration that no convergence test ends takes exactly max_iter updates: *iterations == max_iter.
  * ------------------------------------------------------------------------------------------------ */
+#define PCA_ICP_MAX_ITER 32766
 int64_t pca_icp_workspace_bytes(int32_t max_points);   /* max_points >= max(n_src, n_tgt) */
 int pca_icp_register(pca_ctx *ctx, const float *src_pts /*dev*/, int32_t n_src, const float *tgt_pts /*dev*/,
                      int32_t n_tgt, double max_corr_dist, const double init[16], int max_iter, double rel_fitness,
@@ -998,6 +1002,9 @@ int pca_lanes_to_grid(pca_ctx *ctx, const double *xyz /*dev*/, const int32_t *ve
  *     in host_mask are HOST arrays (what the reference's loader yields: kitti360_obs_dataloader.py:87-106); they are copied
  *     into a pinned block of the context on the staging pool and leave in ONE asynchronous H2D copy; the others are device
  *     pointers.  frame_off[slot] must hold the append position; *evicted / *path_length as pca_host_track_step.
+ *     K1's checks of the frame (pca_kitti_project_sample_filter_ex: sample mode, pts with n > 0, H and W, rgb + sem or
+ *     sem_gt) run FIRST, with pca_k1_defer on as well: a refused frame is neither staged nor noted, the track is not
+ *     stepped and *evicted / *path_length are left alone.
  * pca_kitti_generate_bev  replaces kitti360_sem_pc_accum.py:166-243 + bev_generator.py:63-125 for one un-augmented sample:
  *     ego polylines (pca_host_ego_to_grid on poses - prm->origin; rows / start / *n_rows as there, F = poses of the track
  *     = slot_end - slot_begin), raster (pca_bev_generate_chain, same arguments), and -- host_planes != NULL: page-locked,
@@ -1029,12 +1036,16 @@ int pca_kitti_integrate(pca_ctx *ctx, const pca_kitti_obs *obs, const double P[1
  *     margin; -1 / -1: none); every frame outside [first, last] is certain to fail the raster's crop with all its points.
  * pca_bev_bin_range: the NEXT pca_bev_generate_chain / pca_kitti_generate_bev of the context bins the slots [slot_first,
  *     slot_last_plus1) only (clamped to its window; ignored, and forgotten, if that call writes owed transforms back or is a
- *     different kind of raster).  Results do not change when every frame outside has no point in the view. */
+ *     pca_bev_generate_many).  Results do not change when every frame outside has no point in the view.  A range is good for
+ *     ONE call and never outlives it: the raster takes it and forgets it whether it succeeds or is refused; a
+ *     pca_kitti_generate_bev[_v] that returns -1 before its raster leaves nothing armed; a later pca_bev_bin_range or
+ *     pca_bev_view_hint REPLACES it (slot_last_plus1 < slot_first: nothing is armed). */
 void pca_host_camera_cone(const double P[12], int H, int W, double cone[15]);
 int pca_host_view_hull(int F, const double *then /*[F][12]*/, const float *box /*[F][6]*/, const double *cone /*[15] or NULL*/,
                        const double now[12], const pca_bev_params *prm, int *first, int *last);
 int pca_bev_bin_range(pca_ctx *ctx, int slot_first, int slot_last_plus1);
-/* the two in one call (frame 0 of the F frames sits in slot0): 1 = a narrower range was set, 0 = every frame may reach the view */
+/* the two in one call (frame 0 of the F frames sits in slot0): 1 = a narrower range was set, 0 = every frame may reach the view,
+ * -1 = bad arguments.  The hint replaces whatever was armed before it: after 0 or -1 NO range is armed. */
 int pca_bev_view_hint(pca_ctx *ctx, int slot0, int F, const double *then, const float *box, const double *cone, const double now[12],
                       const pca_bev_params *prm);
 void pca_f32_box_decode(const uint32_t *rows /*[n][6]*/, int n, float *box /*[n][6]: lo x, hi x, lo y, ...; lo > hi = empty*/);
@@ -1076,7 +1087,8 @@ int pca_kitti_generate_bev(pca_ctx *ctx, const pca_store *store, const int64_t *
  * (ctypes: ~0.2 us per converted argument, 45 arguments per step) rewrites the few fields that change -- slot numbers, the
  * pose, the output pointers -- and passes two pointers.  Members as the parameters of the same name; `evicted`, `path_length`,
  * `n_rows` are outputs.  pca_kitti_generate_bev_v also takes the view hint (hint_F > 0: the arguments of pca_bev_view_hint;
- * it is skipped, like the hint itself, when the call writes owed transforms back).  Returns what the plain form returns. */
+ * it is skipped, like the hint itself, when the call writes owed transforms back).  Returns what the plain form returns; a
+ * call that returns -1 -- a bad hint, a refused argument, a refused raster -- leaves no bin range armed for a later raster. */
 typedef struct {
     const pca_kitti_obs *obs; const double *P; int32_t H, W; const uint64_t *filter_mask; const pca_store *store;
     int64_t *frame_off; int32_t slot, sample_mode; pca_host_track *track; const double *T_new_prev; double horizon;

@@ -247,6 +247,7 @@ extern "C" int pca_nusc_sample_filter_transform_ex(pca_ctx *ctx, const double *p
     if (pca_k1_flush_pending(ctx)) return -1;               // a deferred K1 of this context comes first
     if (k1n_check_images(ctx, ncam, H, W, sample_mode)) return -1;
     if (n < 0 || (n > 0 && (!pc || !cam_idx || !imgs || !sems)) || !store || !frame_off) { ctx->err = "k1n: bad arguments"; return -1; }
+    if (!T) { ctx->err = "k1n: T must not be NULL"; return -1; }             // (read on the host, below)
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     const int total = k1n_tiles(n);
@@ -646,6 +647,9 @@ extern "C" int pca_nusc_project_cams(pca_ctx *ctx, const double *pc_lidar, int32
     if (!ctx) return -1;
     if (ncam < 0 || ncam > MAX_CAMS) { ctx->err = "k0n: ncam out of range"; return -1; }
     if (n <= 0) return 0;
+    // (the matrices are read on the host, below; the kernel writes all three outputs for every point)
+    if (!pc_lidar || !T_ego_from_lidar || !T_glob_from_ego || !pc_in_ego || !uv || !cam_idx) { ctx->err = "k0n: bad arguments (pc_lidar, T_ego_from_lidar, T_glob_from_ego and the three outputs are needed)"; return -1; }
+    if (ncam > 0 && (!T_cam_from_glob || !K || !wh)) { ctx->err = "k0n: cameras without T_cam_from_glob, K or wh"; return -1; }
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     K0nArgs a;
@@ -667,6 +671,7 @@ extern "C" int pca_nusc_project_cams(pca_ctx *ctx, const double *pc_lidar, int32
 // K2  in-place re-transform of stored frames (chain of n_T rigid transforms, applied in order)
 // =============================================================================================
 #define MAX_CHAIN 16
+#define K2_MAX_T 65535      // transforms per pca_retransform call (MAX_CHAIN per pass): what pca_retransform_batch_tail takes as frames
 struct K2Args {
     double *x, *y, *z;
     const int64_t *frame_off;
@@ -747,6 +752,7 @@ extern "C" int pca_retransform(pca_ctx *ctx, const pca_store *store, const int64
     if (!ctx) return -1;
     if (pca_k1_flush_pending(ctx)) return -1;               // a deferred K1 of this context comes first
     if (!store || !frame_off || !Ts || n_T < 0 || slot_end < slot_begin) { ctx->err = "k2: bad arguments"; return -1; }
+    if (n_T > K2_MAX_T) { ctx->err = "k2: at most " + std::to_string(K2_MAX_T) + " transforms per call"; return -1; }
     if (n_T == 0 || slot_end == slot_begin) return 0;
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));

@@ -193,13 +193,15 @@ int pca_host_view_hull(int F, const double *then, const float *box, const double
 }
 
 // pca_host_view_hull + pca_bev_bin_range in one call (frame 0 of the F frames sits in slot0).  Returns 1 if a range narrower
-// than the F frames was set, 0 if every frame may reach the view (nothing set), -1 on bad arguments.
+// than the F frames was set, 0 if every frame may reach the view, -1 on bad arguments.  The hint REPLACES whatever range was
+// armed before it: after 0 or -1 nothing is armed (a range left over from another window would bin a sub-window of this one).
 int pca_bev_view_hint(pca_ctx *ctx, int slot0, int F, const double *then, const float *box, const double *cone, const double now[12],
                       const pca_bev_params *prm)
 {
     if (!ctx) return -1;
+    ctx->bin_valid = false;
     int first = 0, last = 0;
-    if (pca_host_view_hull(F, then, box, cone, now, prm, &first, &last)) return -1;
+    if (pca_host_view_hull(F, then, box, cone, now, prm, &first, &last)) { ctx->err = "view_hint: bad arguments (F >= 0; then, now and prm are needed)"; return -1; }
     if (first == 0 && last == F - 1) return 0;
     if (first < 0) { first = 0; last = -1; }
     ctx->bin_first = slot0 + first; ctx->bin_end = slot0 + last + 1; ctx->bin_valid = true;
@@ -357,7 +359,8 @@ const char *pca_last_error(pca_ctx *ctx) { return ctx ? ctx->err.c_str() : "null
 
 int pca_status(pca_ctx *ctx, void *stream, uint32_t *status_out)
 {
-    if (!ctx || !status_out) return -1;
+    if (!ctx) return -1;
+    if (!status_out) { ctx->err = "status: status_out must not be NULL"; return -1; }
     if (pca_k1_flush_pending(ctx)) return -1;               // a deferred K1 of this context comes first
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));

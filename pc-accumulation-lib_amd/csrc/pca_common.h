@@ -156,6 +156,10 @@ static inline bool pca_small_copy() { return PCA_ENV_ONCE("PCA_SMALL_COPY", 0) !
 // internal (pca_k1.hip): runs a deferred K1 now, on its own (no-op without one).  Every entry point that reads or writes a
 // store, frame_off or the status word calls it first.
 int pca_k1_flush_pending(pca_ctx *ctx);
+// internal (pca_k1.hip): K1's host-side checks of a call's frames (sample mode, pointers, image size, every frame); 0, or -1
+// with ctx->err set.  Nothing is launched, staged or noted.
+int pca_k1_check_frames(pca_ctx *ctx, const pca_kitti_frame *frames, int n_frames, const double *P, int H, int W,
+                        const pca_store *store, const int64_t *frame_off, int sample_mode);
 // internal (pca_api.hip)
 // The regions of every workspace start on 256-byte boundaries.
 static inline int64_t pca_align256(int64_t v) { return (v + 255) & ~255ll; }

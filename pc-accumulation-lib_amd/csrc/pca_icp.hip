@@ -89,16 +89,20 @@ static_assert(ICP_ST_T_PREV >= ICP_ST_INIT && ICP_ST_T_PREV + 12 <= ICP_ST_DBG &
 static_assert(ICP_ST_SUMS >= ICP_ST_CLEARED && ICP_ST_SUMS + ICP_NACC <= ICP_ST_SIZE, "the sums end inside the block");
 static_assert(ICP_ST_MIRRORED <= ICP_HOST_NEWS && ICP_HOST_NEWS < ICP_HOST_SIZE, "the news word lies behind the mirrored range");
 
-// The news word: tag of the registration | ended << 8 | passes done.  icp_solve_step packs it, the host's poller
-// (IcpNews) unpacks it.  The passes have eight bits: pass + 1 must stay below 256, so with max_iter >= 255 the count runs
-// into the ended bit and reads as an end.  The call counter behind the tag wraps at 24 bits.
+// The news word: tag of the registration | ended << 15 | passes done.  icp_solve_step packs it, the host's poller
+// (IcpNews) unpacks it.  The 16 bits below the tag: `ended` at the top, the passes in the 15 below it.  A registration runs
+// max_iter + 1 passes (the last one only evaluates), so max_iter <= PCA_ICP_MAX_ITER = 2^15 - 2 keeps the count inside its
+// field (pca_icp_register refuses more).  The call counter behind the tag wraps at 24 bits.
+#define ICP_NEWS_ENDED 0x8000ull
+#define ICP_NEWS_PASSES 0x7fffull
+static_assert(PCA_ICP_MAX_ITER + 1 <= (int)ICP_NEWS_PASSES, "every pass count of a registration fits the news word");
 struct IcpNewsWord { uint64_t tag; bool ended; int passes; };
 __host__ __device__ inline uint64_t icp_news_tag(uint32_t call) { return (uint64_t)call << 16; }
 __host__ __device__ inline uint64_t icp_news_pack(uint64_t tag, bool ended, int passes)
 {
-    return tag | (ended ? 0x100ull : 0ull) | (uint64_t)passes;
+    return tag | (ended ? ICP_NEWS_ENDED : 0ull) | ((uint64_t)passes & ICP_NEWS_PASSES);
 }
-__host__ __device__ inline IcpNewsWord icp_news_unpack(uint64_t w) { return {w & ~0xffffull, (w & 0x100u) != 0, (int)(w & 0xffu)}; }
+__host__ __device__ inline IcpNewsWord icp_news_unpack(uint64_t w) { return {w & ~0xffffull, (w & ICP_NEWS_ENDED) != 0, (int)(w & ICP_NEWS_PASSES)}; }
 
 struct IcpGrid {
     uint32_t *cnt;               // [cells] points per cell (counting pass), all zero again after the fill pass
@@ -1292,6 +1296,7 @@ int pca_icp_register(pca_ctx *ctx, const float *src_pts, int32_t n_src, const fl
     if (!src_pts || !tgt_pts || n_src < 1 || n_tgt < 1 || !workspace || !T_out) { ctx->err = "icp: bad arguments"; return -1; }
     if (workspace_bytes < pca_icp_workspace_bytes(n_tgt > n_src ? n_tgt : n_src)) { ctx->err = "icp: workspace too small"; return -1; }
     if (max_iter < 1) max_iter = 30;
+    if (max_iter > PCA_ICP_MAX_ITER) { ctx->err = "icp: max_iter must not exceed " + std::to_string(PCA_ICP_MAX_ITER); return -1; }
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     IcpArgs a;

@@ -339,17 +339,26 @@ static int k1_launch(pca_ctx *ctx, const K1Call &c, const K1Plan *plan, bool fus
 }
 
 // ---- the steps of pca_kitti_project_sample_filter_ex ----
-static int k1_validate(pca_ctx *ctx, const K1Call &c, const pca_kitti_frame *frames, int n_frames)
+// K1's checks of a call's frames, the ONE place that knows them: pca_kitti_project_sample_filter_ex runs them before it plans,
+// pca_kitti_integrate before it stages, notes (pca_k1_defer) or steps anything -- a noted frame goes to the GPU unchecked
+// (pca_k1_prepare_pending).
+int pca_k1_check_frames(pca_ctx *ctx, const pca_kitti_frame *frames, int n_frames, const double *P, int H, int W,
+                        const pca_store *store, const int64_t *frame_off, int sample_mode)
 {
-    if (c.sample_mode != PCA_SAMPLE_NEAREST && c.sample_mode != PCA_SAMPLE_BILINEAR) { ctx->err = "k1: unknown sample_mode"; return -1; }
-    if (!frames || n_frames <= 0 || !c.store || !c.frame_off || !c.P) { ctx->err = "k1: bad arguments"; return -1; }
-    if (c.H < 0 || c.W < 0 || (int64_t)c.H * c.W * 3 >= (1ll << 31)) { ctx->err = "k1: image too large"; return -1; }
+    if (sample_mode != PCA_SAMPLE_NEAREST && sample_mode != PCA_SAMPLE_BILINEAR) { ctx->err = "k1: unknown sample_mode"; return -1; }
+    if (!frames || n_frames <= 0 || !store || !frame_off || !P) { ctx->err = "k1: bad arguments"; return -1; }
+    if (H < 0 || W < 0) { ctx->err = "k1: H and W must not be negative"; return -1; }
+    if ((int64_t)H * W * 3 >= (1ll << 31)) { ctx->err = "k1: image too large"; return -1; }
     for (int k = 0; k < n_frames; ++k) {
         const pca_kitti_frame &f = frames[k];
-        if (f.n < 0 || (f.n > 0 && !f.pts)) { ctx->err = "k1: bad frame"; return -1; }
-        if (!f.sem_gt && f.n > 0 && (!f.rgb || !f.sem || c.H * c.W == 0)) { ctx->err = "k1: frame needs rgb+sem or sem_gt"; return -1; }
+        if (f.n < 0 || (f.n > 0 && !f.pts)) { ctx->err = "k1: bad frame (n < 0, or points without pts)"; return -1; }
+        if (!f.sem_gt && f.n > 0 && (!f.rgb || !f.sem || (int64_t)H * W == 0)) { ctx->err = "k1: frame needs rgb+sem or sem_gt"; return -1; }
     }
     return 0;
+}
+static int k1_validate(pca_ctx *ctx, const K1Call &c, const pca_kitti_frame *frames, int n_frames)
+{
+    return pca_k1_check_frames(ctx, frames, n_frames, c.P, c.H, c.W, c.store, c.frame_off, c.sample_mode);
 }
 // The colour gather is one 4-byte load per point: a one-pixel image (3 bytes) is handed to the kernel as a 4-byte copy (*frames: then `padded`)
 static int k1_pad_tiny_images(pca_ctx *ctx, const K1Call &c, const pca_kitti_frame **frames, int n_frames, std::vector<pca_kitti_frame> *padded)

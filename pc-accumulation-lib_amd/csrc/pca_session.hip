@@ -24,6 +24,14 @@ int pca_kitti_integrate(pca_ctx *ctx, const pca_kitti_obs *obs, const double P[1
     if (!ctx) return -1;
     if (!obs || obs->n < 0 || !P || !filter_mask || !store || !frame_off) { ctx->err = "kitti_integrate: bad arguments"; return -1; }
     if (track && (!T_new_prev || !evicted || !path_length)) { ctx->err = "kitti_integrate: the pose track needs T_new_prev and its outputs"; return -1; }
+    // K1's own checks, on the frame as the caller describes it (a host array counts as present: it is staged below), BEFORE
+    // anything is staged, noted or stepped: a deferred K1 is not looked at again until it runs inside a raster.
+    {
+        pca_kitti_frame asked;
+        asked.pts = (const float *)obs->pts; asked.rgb = (const uint8_t *)obs->rgb; asked.sem = (const uint8_t *)obs->sem;
+        asked.sem_gt = (const uint8_t *)obs->sem_gt; asked.n = obs->n; asked.reserved = 0;
+        if (pca_k1_check_frames(ctx, &asked, 1, P, H, W, store, frame_off, sample_mode)) return -1;
+    }
     hipStream_t s = (hipStream_t)stream;
     PCA_CHECK(ctx, hipSetDevice(ctx->device));
     if (pca_k1_flush_pending(ctx)) return -1;               // the frame before this one, if its K1 is still owed
@@ -126,9 +134,26 @@ int pca_kitti_generate_bev(pca_ctx *ctx, const pca_store *store, const int64_t *
                            double *traj_rows, int32_t *traj_start, int32_t *n_rows, void *stream)
 {
     if (!ctx) return -1;
-    if (!prm || !planes_f16 || !track || !traj_rows || !traj_start || !n_rows) { ctx->err = "kitti_generate_bev: bad arguments"; return -1; }
+    // (a call refused here leaves no bin range armed: the raster that would have taken and cleared it does not run, and the
+    // context's next raster may be of another window)
+    if (!prm || !planes_f16 || !track || !traj_rows || !traj_start || !n_rows) {
+        ctx->bin_valid = false;
+        ctx->err = "kitti_generate_bev: bad arguments (prm, planes_f16, track, traj_rows, traj_start and n_rows are needed)";
+        return -1;
+    }
     const int64_t F = pca_host_track_len(track);
-    if (F != slot_end - slot_begin) { ctx->err = "kitti_generate_bev: the pose track and the window disagree about the number of frames"; return -1; }
+    if (F != slot_end - slot_begin) {
+        ctx->bin_valid = false;
+        ctx->err = "kitti_generate_bev: the pose track and the window disagree about the number of frames";
+        return -1;
+    }
+    if (pca_bev_generate_chain(ctx, store, nullptr, frame_off, slot_begin, slot_split, slot_end, max_points, prm, pending_Ts,
+                               pending_slot_ends, n_pending, write_back, workspace, workspace_bytes, nullptr, planes_f16,
+                               nullptr, stream) != 0)
+        return -1;
+    const int ticket = host_planes ? pca_host_d2h_async(ctx, planes_f16, host_planes, 21ll * prm->px * prm->px * 2, stream) : 0;
+    if (ticket < 0) return -1;
+    // (the polylines last, while the device works: a call that is refused writes none of its outputs)
     // rel = poses - origin, element by element (numpy: poses - origin), then the reference's trajectory transform
     static thread_local std::vector<double> rel;
     rel.resize((size_t)(3 * (F > 0 ? F : 1)));
@@ -136,12 +161,7 @@ int pca_kitti_generate_bev(pca_ctx *ctx, const pca_store *store, const int64_t *
     for (int64_t f = 0; f < F; ++f)
         for (int k = 0; k < 3; ++k) rel[(size_t)(3 * f + k)] = Hp[4 * f + k] - prm->origin[k];
     *n_rows = pca_host_ego_to_grid(rel.data(), (int)F, prm->R, prm->dx, prm->dy, prm->view, prm->px, traj_rows, traj_start);
-    if (pca_bev_generate_chain(ctx, store, nullptr, frame_off, slot_begin, slot_split, slot_end, max_points, prm, pending_Ts,
-                               pending_slot_ends, n_pending, write_back, workspace, workspace_bytes, nullptr, planes_f16,
-                               nullptr, stream) != 0)
-        return -1;
-    if (!host_planes) return 0;
-    return pca_host_d2h_async(ctx, planes_f16, host_planes, 21ll * prm->px * prm->px * 2, stream);
+    return ticket;
 }
 
 int pca_kitti_integrate_v(pca_ctx *ctx, pca_kitti_integrate_args *a)
@@ -159,7 +179,7 @@ int pca_kitti_generate_bev_v(pca_ctx *ctx, pca_kitti_generate_bev_args *a)
     a->hinted = 0;
     if (a->hint_F > 0 && !(a->n_pending > 0 && a->write_back)) {
         const int rc = pca_bev_view_hint(ctx, a->hint_slot0, a->hint_F, a->hint_then, a->hint_box, a->hint_cone, a->hint_now, a->prm);
-        if (rc < 0) { ctx->err = "kitti_generate_bev_v: bad view hint"; return -1; }
+        if (rc < 0) { ctx->err = "kitti_generate_bev_v: bad view hint"; return -1; }   // (the hint has cleared the range)
         a->hinted = rc;
     }
     return pca_kitti_generate_bev(ctx, a->store, a->frame_off, a->slot_begin, a->slot_split, a->slot_end, a->max_points, a->prm,
