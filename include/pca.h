@@ -1056,6 +1056,10 @@ void pca_f32_box_decode(const uint32_t *rows /*[n][6]*/, int n, float *box /*[n]
  *     the window, or what pca_bev_bin_range / pca_bev_view_hint left of it}.  G == the device's compute units with a bin range
  *     set: a one-round launch.  0 / -1. */
 int pca_debug_bev_level1(const pca_ctx *ctx, int out[4]);
+/* pca_debug_bev_lds: level 1's LDS as the PROCESS's last pca_bev_generate_chain launched it (process-wide: read it before another
+ *     context of the process rasters): out = {points per thread parked in LDS behind the register points (0, or 4 where the
+ *     CU's LDS has room; PCA_BEV_LDS_P=0: always 0), bytes of dynamic LDS: histogram + cursors + the parked block}.  0 / -1. */
+int pca_debug_bev_lds(int out[2]);
 /* pca_debug_icp_layout: where a pca_icp_register(n_src, n_tgt) leaves its intermediate results in the caller's workspace
  *     (host only; nothing is launched).  out[0..11]: byte offsets, from the workspace's base rounded up to 256, of start[0],
  *     spts[0] (coarse grid), start[1], spts[1] (fine grid), normal, nn_prev, nn_cell, nn_slack, partial, zr_part, state, and the

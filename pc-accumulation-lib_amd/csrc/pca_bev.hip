@@ -43,6 +43,12 @@
 #ifndef BIN_REG_P
 #define BIN_REG_P 12              // points per thread of level 1 that stay in registers between its passes (a multiple of 4)
 #endif
+#ifndef BIN_LDS_P
+#define BIN_LDS_P 4               // ... and beyond them, points per thread whose key and z are parked in LDS between the passes (<= BIN_REG_P)
+#endif
+#ifndef BIN_LUNR
+#define BIN_LUNR 2                // ... worked on this many per thread at a time in pass A
+#endif
 #ifndef C_THREADS
 #define C_THREADS 256             // workgroup size of the tile kernel
 #endif
@@ -105,6 +111,8 @@ struct alignas(16) BevArgs {                             // (16: pca_fetch_block
     int dbg;
     int band_r0, band_rows;   // banded rasters (px > 1024, the bev_*_band kernels): the band's first tile row and its tile rows;
                           // T = band_rows * tx tiles, numbered from the band's first row.  Unused by the whole-grid kernels.
+    int lds_p;            // points per thread that level 1 parks in LDS behind its register points (0 or BIN_LDS_P: bev_decide_lds_p).
+                          // Last, so that every field above keeps its offset (level 1's scalar spills follow the offsets)
 };
 #define HQ_CLASSES 32
 #define HQ_CURSOR 32
@@ -203,8 +211,10 @@ __device__ __forceinline__ void bin_store(const BevArgs &a, const uint32_t *dynb
 
 // The first REG_P * 1024 points of a chunk stay in REGISTERS between the passes (key and stored z; colour and intensity of
 // the kept points are gathered at the start of pass B, all of a lane's gathers back to back), so pass B is LDS cursors and
-// 16-byte stores.  A 200-frame KITTI window is ~10 000 points per chunk: all of it.  Whatever a chunk holds beyond that
-// (giant windows) takes the memory path: keys to the key buffer, re-read with z / intensity / colour in pass B.
+// 16-byte stores.  A 200-frame KITTI window is ~10 000 points per chunk: all of it.  The next a.lds_p * 1024 points (a one-round
+// launch makes pieces of ~14 000) are PARKED IN LDS, key and transformed z, and handled like the register points in both passes
+// (profiles/bev_level1_lds_overflow.txt).  Whatever a chunk holds beyond that (giant windows) takes the memory path: keys to the
+// key buffer, re-read with z / intensity / colour in pass B.
 __device__ unsigned long long g_dbg_stamps[1024][8];   // PCA_BEV_DBG=8|16|32: per-tile / per-chunk phase stamps (diagnostics)
 #define BIN_STAMP(slot) do { if ((a.dbg & 32) && threadIdx.x == 0 && blockIdx.x < 1024) g_dbg_stamps[blockIdx.x][slot] = wall_clock64(); } while (0)
 // exclusive scan of a level-1 workgroup's histogram over the tiles (thread t owns `per` consecutive tiles): LDS cursors and the
@@ -286,7 +296,15 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     __syncthreads();
     const PendHi pend_hi = owed_bounds(a.owed, a.frame_off, a.slot_begin, w.lo);
     const int64_t reg_hi = w.c_lo + (int64_t)REG_P * AB_THREADS < w.c_hi ? w.c_lo + (int64_t)REG_P * AB_THREADS : w.c_hi;
-    // ---- pass A, register part ----
+    // The next lds_p * 1024 points of the chunk are RESIDENT too: their (key, transformed z) wait in LDS behind the cursors, [j][thread]
+    // (a wave reads and writes consecutive words: no bank conflicts), so that a piece a little larger than the registers -- a
+    // one-round launch cuts the visible window into pieces of ~14 k points -- stays off the memory path below.
+    const int lds_p = REG_P > 0 ? a.lds_p : 0;
+    const int64_t res_cap = (int64_t)(REG_P + lds_p) * AB_THREADS;
+    const int64_t res_hi = w.c_lo + res_cap < w.c_hi ? w.c_lo + res_cap : w.c_hi;
+    double *s_pz = reinterpret_cast<double *>(s_lds + 2 * n_hist);     // [lds_p][AB_THREADS] (8 n_hist bytes in: aligned)
+    uint32_t *s_pk = reinterpret_cast<uint32_t *>(s_pz + lds_p * AB_THREADS);   // [lds_p][AB_THREADS]
+    // ---- pass A, resident part (registers, then LDS) ----
     // Every load is issued by every lane, in straight-line code: a lane past the end of the chunk reads the chunk's first
     // point instead.  (Loads inside divergent branches leave the compiler without a count of what is in flight; it then
     // waits for EVERYTHING before the next use, which serialised the four points of a batch into four memory round trips.)
@@ -296,10 +314,12 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     float rinten[REG_P > 0 ? REG_P : 1];
     double rz[REG_P > 0 ? REG_P : 1];
     const uint32_t n_reg = w.c_lo < reg_hi ? (uint32_t)(reg_hi - w.c_lo) : 0u;
-    auto rel = [&](int64_t p) -> uint32_t {                 // position p relative to the chunk, clamped to [0, n_reg]
+    const uint32_t n_res = w.c_lo < res_hi ? (uint32_t)(res_hi - w.c_lo) : 0u;      // (= n_reg unless points are parked in LDS)
+    auto rel = [&](int64_t p) -> uint32_t {                 // position p relative to the chunk, clamped to [0, n_res]
         const int64_t d = p - w.c_lo;
-        return d <= 0 ? 0u : (d < (int64_t)n_reg ? (uint32_t)d : n_reg);
+        return d <= 0 ? 0u : (d < (int64_t)n_res ? (uint32_t)d : n_res);
     };
+    const int n_park_rows = (int)((n_res - n_reg + AB_THREADS - 1) / AB_THREADS);    // rows of the parked block in use (<= lds_p)
     const uint32_t sp_rel = rel(w.sp);                      // lanes i >= sp_rel are 'future' points
     if (REG_P > 0 && n_reg > 0) {
         const double *xb = a.st.x + w.c_lo, *yb = a.st.y + w.c_lo, *zb = a.st.z + w.c_lo;
@@ -311,22 +331,26 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
         // contiguous chunks, to even out their run times: every workgroup then pays the kept-point work, +4 us.)
         double XA[UNR], YA[UNR], ZA[UNR];
         uint32_t DA[UNR];
-        auto issue = [&](int j0, double (&X)[UNR], double (&Y)[UNR], double (&Z)[UNR], uint32_t (&D)[UNR]) {
+        // (both take batches of any size N: the register points go by UNR, the parked points by BIN_LUNR)
+        auto issue = [&](int j0, auto &X, auto &Y, auto &Z, auto &D) {
+            constexpr int N = (int)(sizeof(D) / sizeof(D[0]));
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x, ic = i < n_reg ? i : 0u;
+            for (int u = 0; u < N; ++u) {
+                const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x, ic = i < n_res ? i : 0u;
                 X[u] = xb[ic];
                 Y[u] = yb[ic];
                 Z[u] = zb[ic];
                 D[u] = db[ic];
             }
         };
-        auto work = [&](int j0, double (&X)[UNR], double (&Y)[UNR], double (&Z)[UNR], uint32_t (&D)[UNR]) {
+        // keep(u, key, z): where point j0 + u of the lane waits for pass B -- a register pair, or its slot of the parked block
+        auto work = [&](int j0, auto &X, auto &Y, auto &Z, auto &D, auto &&keep) {
+            constexpr int N = (int)(sizeof(D) / sizeof(D[0]));
             // the owed re-transforms, oldest first, each a separate fma chain (the roundings of one K2 pass per transform):
             // the same chain as apply_owed of pca_bev_view.h, in a form tuned for this path (docs/history.md, "BEV level 1, round 3").
             // Transform k's twelve coefficients are fetched (scalar loads) when its turn comes instead of all forty-eight
             // living in scalar registers through the whole pass; applied branch-free: all but the newest frames' points
-            // owe every pending transform, and UNR independent chains interleave.
+            // owe every pending transform, and N independent chains interleave.
             uint32_t n_moved = 0;                           // lanes i < n_moved were moved by some transform
 #pragma unroll 1
             for (int k = 0; k < a.owed.n_pend; ++k) {
@@ -337,11 +361,11 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
                 const double t0 = Tk.m[0], t1 = Tk.m[1], t2 = Tk.m[2], t3 = Tk.m[3], t4 = Tk.m[4], t5 = Tk.m[5], t6 = Tk.m[6],
                              t7 = Tk.m[7], t8 = Tk.m[8], t9 = Tk.m[9], t10 = Tk.m[10], t11 = Tk.m[11];
                 // (uniform) every point of this batch owes it -- all but the batches that reach into the newest frames: no selects
-                const uint32_t batch_end = (uint32_t)(j0 + UNR) * AB_THREADS < n_reg ? (uint32_t)(j0 + UNR) * AB_THREADS : n_reg;
+                const uint32_t batch_end = (uint32_t)(j0 + N) * AB_THREADS < n_res ? (uint32_t)(j0 + N) * AB_THREADS : n_res;
                 const bool all_owe = n_owe >= batch_end;
                 if (all_owe) {
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
+                    for (int u = 0; u < N; ++u) {
                         const double nx = fma(t2, Z[u], fma(t1, Y[u], t0 * X[u])) + t3;
                         const double ny = fma(t6, Z[u], fma(t5, Y[u], t4 * X[u])) + t7;
                         const double nz = fma(t10, Z[u], fma(t9, Y[u], t8 * X[u])) + t11;
@@ -349,7 +373,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
                     }
                 } else {
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
+                    for (int u = 0; u < N; ++u) {
                         const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x;
                         const bool owed = i < n_owe;
                         const double nx = fma(t2, Z[u], fma(t1, Y[u], t0 * X[u])) + t3;
@@ -362,23 +386,38 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
             if (a.owed.write_back && n_moved > 0) {
                 double *xw = a.st.x + w.c_lo, *yw = a.st.y + w.c_lo, *zw = a.st.z + w.c_lo;
 #pragma unroll
-                for (int u = 0; u < UNR; ++u) {
+                for (int u = 0; u < N; ++u) {
                     const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x;
                     if (i < n_moved) { xw[i] = X[u]; yw[i] = Y[u]; zw[i] = Z[u]; }
                 }
             }
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) {
+            for (int u = 0; u < N; ++u) {
                 const uint32_t i = (uint32_t)(j0 + u) * AB_THREADS + threadIdx.x;
-                rkey[j0 + u] = view_key_lean<BAND>(vc, X[u], Y[u], Z[u], i < n_reg && D[u] != 1u, i >= sp_rel ? 1u : 0u);
-                rz[j0 + u] = Z[u];
-                if (rkey[j0 + u] != KEY_INVALID) atomicAdd(&s_h[rkey[j0 + u] >> hs], 1u);
+                const uint32_t key = view_key_lean<BAND>(vc, X[u], Y[u], Z[u], i < n_res && D[u] != 1u, i >= sp_rel ? 1u : 0u);
+                keep(u, key, Z[u]);
+                if (key != KEY_INVALID) atomicAdd(&s_h[key >> hs], 1u);
             }
         };
 #pragma unroll
         for (int j0 = 0; j0 < REG_P; j0 += UNR) {
             issue(j0, XA, YA, ZA, DA);
-            work(j0, XA, YA, ZA, DA);
+            work(j0, XA, YA, ZA, DA, [&](int u, uint32_t key, double z) { rkey[j0 + u] = key; rz[j0 + u] = z; });
+        }
+        // the parked points, in the same form, by batches of BIN_LUNR rows of the block and only the rows the piece reaches (a
+        // one-round piece of 14 100 points: two of the four).  Every slot of such a row is written: a lane past the chunk's end
+        // parks KEY_INVALID.
+        if (n_park_rows > 0) {                              // (uniform)
+            double XL[BIN_LUNR], YL[BIN_LUNR], ZL[BIN_LUNR];
+            uint32_t DL[BIN_LUNR];
+#pragma unroll
+            for (int jl = 0; jl < BIN_LDS_P; jl += BIN_LUNR) {
+                if (jl >= n_park_rows) break;               // (uniform)
+                issue(REG_P + jl, XL, YL, ZL, DL);
+                work(REG_P + jl, XL, YL, ZL, DL, [&](int u, uint32_t key, double z) {
+                    if (jl + u < lds_p) { s_pk[(jl + u) * AB_THREADS + threadIdx.x] = key; s_pz[(jl + u) * AB_THREADS + threadIdx.x] = z; }
+                });
+            }
         }
     } else {
 #pragma unroll
@@ -388,7 +427,7 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
     // ---- pass A, memory part (what the chunk holds beyond the registers) ----
     constexpr int MUNR = BIN_UNR;
     const ViewConst vcm = view_const(a.prm, a.tx, a.band_r0, a.band_rows);
-    for (int64_t base = reg_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
+    for (int64_t base = res_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
         double X[MUNR], Y[MUNR], Z[MUNR];
         uint8_t D[MUNR];
 #pragma unroll
@@ -448,10 +487,35 @@ __device__ __forceinline__ void bev_tile_bin_body(const BevArgs &a)
             const uint32_t pos = seg + atomicAdd(&s_cur[rkey[j] >> hs], 1u);
             bin_store<I64>(a, s_dyn, pos, rkey[j], rrgb[j], rz[j], 0.0, rinten[j]);
         }
+        // ... then the parked points, in the registers the records above have left: keys out of LDS, all gathers back to back,
+        // z out of LDS at the store.  x, y, z are not read again and no transform is applied again.
+        if (n_park_rows > 0) {                              // (uniform)
+            constexpr int LP = BIN_LDS_P < REG_P ? BIN_LDS_P : REG_P;
+#pragma unroll
+            for (int j = 0; j < LP; ++j) {
+                rkey[j] = s_pk[(j < n_park_rows ? j : 0) * AB_THREADS + threadIdx.x];
+                if (j >= n_park_rows) rkey[j] = KEY_INVALID;      // (a row the piece does not reach was not written)
+                const uint32_t i = (uint32_t)(REG_P + j) * AB_THREADS + threadIdx.x, ic = rkey[j] != KEY_INVALID ? i : 0u;
+                rrgb[j] = cb[ic];
+                rinten[j] = ib[ic];
+            }
+            {
+                uint32_t touch = 0;
+#pragma unroll
+                for (int j = 0; j < LP; ++j) touch |= rrgb[j] ^ __float_as_uint(rinten[j]);
+                asm volatile("" ::"v"(touch));
+            }
+#pragma unroll
+            for (int j = 0; j < LP; ++j) {
+                if (rkey[j] == KEY_INVALID) continue;
+                const uint32_t pos = seg + atomicAdd(&s_cur[rkey[j] >> hs], 1u);
+                bin_store<I64>(a, s_dyn, pos, rkey[j], rrgb[j], s_pz[j * AB_THREADS + threadIdx.x], 0.0, rinten[j]);
+            }
+        }
     }
     BIN_STAMP(4);
     const bool stale = a.owed.n_pend > 0 && !a.owed.write_back;
-    for (int64_t base = reg_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
+    for (int64_t base = res_hi + threadIdx.x; base < w.c_hi; base += MUNR * AB_THREADS) {
         uint32_t key[MUNR], pos[MUNR], rgbs[MUNR];
         double zz[MUNR], iv[MUNR], xs[MUNR], ys[MUNR];
 #pragma unroll
@@ -1644,6 +1708,7 @@ static BevLayout bev_layout(int64_t max_points, int px)
     return l;
 }
 
+static int g_last_lds[2] = {0, 0};   // diagnostics (pca_debug_bev_lds): lds_p and level 1's dynamic LDS of the process's last pca_bev_generate_chain
 // Every kernel of the rasteriser the host can launch, by (I64, BAND): g_bev_kernels[intensity64 given][banded raster].
 // bev_set_lds_attributes walks this table, so a kernel that can be launched is a kernel whose LDS ceiling is set.
 // (bev_tile_bin_k1, level 1 with a riding K1, stands next to it: !I64, whole grid only, K1_RIDE_LDS.)
@@ -1655,6 +1720,15 @@ struct BevKernelSet {
     int bin_lds;                                            // ceiling of level 1's dynamic LDS [bytes]; the heavy kernels': HEAVY_LDS_BYTES
 };
 #define K1_RIDE_LDS (80 * 1024)
+// Level 1's LDS budget.  A CU has 160 KiB and level 1 runs one workgroup per CU whatever it asks for.  Its static part: a few words
+// of its own (BIN_STATIC_LDS bounds them), and with a riding K1 k1_body's candidate buffers on top (K1_RIDE_STATIC_LDS bounds the
+// kernel's whole static block, 74 240 B).  Its dynamic part: histogram + cursors, then the parked block, 12 bytes per point.
+#define LDS_CU (160 * 1024)
+#define BIN_STATIC_LDS 256
+#define K1_RIDE_STATIC_LDS 74240
+#define BIN_PARK_BYTES(lds_p) ((size_t)(lds_p) * AB_THREADS * 12)
+static_assert(BIN_LDS_P >= 0 && BIN_LDS_P <= BIN_REG_P, "pass B handles the parked points in the register points' registers");
+static_assert(K1_RIDE_LDS <= LDS_CU - K1_RIDE_STATIC_LDS, "a riding K1's static LDS and the largest histogram share a CU");
 #define BEV_WHOLE_SET(I)                                                                                                          \
     { bev_tile_bin<I>, bev_tile_cells<I>,                                                                                         \
       {{bev_tile_cells_heavy<I, false, false>, bev_tile_cells_heavy<I, false, true>}, {bev_tile_cells_heavy<I, true, false>, bev_tile_cells_heavy<I, true, true>}}, \
@@ -1732,6 +1806,7 @@ static int bev_prepare(pca_ctx *ctx, const pca_store *store, const double *inten
     a.bh0 = reinterpret_cast<uint32_t *>(w + l.bh0);
     a.split = 0;
     a.Gk = 0; a.k1_slot = -1; a.k1_n = 0;
+    a.lds_p = 0;                                            // (bev_decide_lds_p)
     a.bin_first = slot_begin; a.bin_end = slot_end;
     a.heavy = reinterpret_cast<uint32_t *>(w + l.heavy);
     a.recs = w + l.recs;
@@ -1755,12 +1830,14 @@ static int bev_set_lds_attributes(pca_ctx *ctx)
     auto grant = [](auto k, size_t bytes) { return k ? hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess; };
     for (int i = 0; i < 4; ++i) {
         const BevKernelSet &ks = g_bev_kernels[i >> 1][i & 1];
-        PCA_CHECK(ctx, grant(ks.bin, ks.bin_lds));
-        PCA_CHECK(ctx, grant(ks.bin_many, ks.bin_lds));
+        // (histogram + cursors up to bin_lds, the parked block behind them where the CU has room: bev_decide_lds_p)
+        const size_t room = LDS_CU - BIN_STATIC_LDS, most = ks.bin_lds + BIN_PARK_BYTES(BIN_LDS_P);
+        PCA_CHECK(ctx, grant(ks.bin, most < room ? most : room));
+        PCA_CHECK(ctx, grant(ks.bin_many, most < room ? most : room));
         for (int v = 0; v < 4; ++v) PCA_CHECK(ctx, grant(ks.heavy[v >> 1][v & 1], HEAVY_LDS_BYTES));
         PCA_CHECK(ctx, grant(ks.heavy_many, HEAVY_LDS_BYTES));
     }
-    PCA_CHECK(ctx, grant(bev_tile_bin_k1, K1_RIDE_LDS));
+    PCA_CHECK(ctx, grant(bev_tile_bin_k1, LDS_CU - K1_RIDE_STATIC_LDS));
     lds_set = true;
     return 0;
 }
@@ -1824,6 +1901,16 @@ static int bev_decide_k1_ride(pca_ctx *ctx, const BevArgs &a, bool tuned, size_t
     return pca_k1_flush_pending(ctx);
 }
 
+// Parked points: BIN_LDS_P per thread if level 1's static LDS (with the riding K1's, if one rides), its histogram and cursors
+// (`lds` bytes) and the parked block still fit the CU, else none -- a piece beyond the registers then takes the memory path, as
+// ever.  Not for f64 intensities (no register path).  PCA_BEV_LDS_P=0: never (A/B; same results).
+static int bev_decide_lds_p(const void *intensity64, size_t lds, bool k1_rides)
+{
+    if (intensity64 || BIN_LDS_P == 0 || !PCA_ENV_ONCE("PCA_BEV_LDS_P", 1)) return 0;
+    const size_t fixed = k1_rides ? K1_RIDE_STATIC_LDS : BIN_STATIC_LDS;
+    return fixed + lds + BIN_PARK_BYTES(BIN_LDS_P) <= LDS_CU ? BIN_LDS_P : 0;
+}
+
 // Bin range and one-round size; returns the workgroups of a one-round launch of level 1, 0: no such launch.
 struct BevBinRange { bool given; int first, end; };        // (pca_bev_bin_range, as the call found it in the context)
 static int bev_decide_bin_range(pca_ctx *ctx, BevArgs &a, bool tuned, const BevBinRange &r)
@@ -1867,6 +1954,7 @@ static void bev_size_level1(pca_ctx *ctx, BevArgs &a, int nt, int one_round)
 // call, and hipExtAnyOrderLaunch is not honoured on gfx9 -- see DESIGN.md.)
 static int bev_launch_raster(pca_ctx *ctx, const BevKernelSet &ks, const BevArgs &a, const K1Args *k1, size_t lds, hipStream_t s)
 {
+    lds += BIN_PARK_BYTES(a.lds_p);                         // (the parked block lies behind the histogram and the cursors)
     if (k1) {
         PCA_LAUNCH_SHM(ctx, PCA_K_BEV_BIN, bev_tile_bin_k1, dim3(a.G), dim3(AB_THREADS), lds, s, a, *k1);
         pca_k1_pending_launched(ctx, s);
@@ -1906,6 +1994,8 @@ int pca_bev_generate_chain(pca_ctx *ctx, const pca_store *store, const double *i
     bev_decide_heavy(ctx, a, tuned);
     const size_t lds = bev_decide_split(a, tuned);
     if (bev_decide_k1_ride(ctx, a, tuned, lds, s, &k1a, &nt)) return -1;
+    a.lds_p = bev_decide_lds_p(intensity64, lds, nt > 0);
+    g_last_lds[0] = a.lds_p; g_last_lds[1] = (int)(lds + BIN_PARK_BYTES(a.lds_p));
     const int one_round = bev_decide_bin_range(ctx, a, tuned, bin_range);
     bev_size_level1(ctx, a, nt, one_round);
     ctx->last_level1[0] = a.G; ctx->last_level1[1] = a.Gk; ctx->last_level1[2] = a.bin_first; ctx->last_level1[3] = a.bin_end;
@@ -1977,7 +2067,9 @@ int pca_bev_generate_many(pca_ctx *ctx, const pca_store *store, const double *in
             bev_set_band(d, b * rows);
         }
     if (bev_set_lds_attributes(ctx)) return -1;
-    const size_t lds = (size_t)l.T * 8;                     // (the largest band's)
+    const int lds_p = bev_decide_lds_p(intensity64, (size_t)l.T * 8, false);
+    for (int64_t k = 0; k < (int64_t)n_jobs * n_bands; ++k) ha[k].lds_p = lds_p;
+    const size_t lds = (size_t)l.T * 8 + BIN_PARK_BYTES(lds_p);     // (the largest band's histogram and cursors, then the parked block)
     // The argument blocks live in ONE constant array per device (g_bev_many): a call on another stream or from another
     // context of this device must not overwrite it while this call's kernels may still read it.  Calls take turns on the
     // host (mutex) and on the device (every call first waits for the event the previous one recorded behind its kernels).
@@ -2063,6 +2155,15 @@ int pca_bev_warp(pca_ctx *ctx, const uint16_t *planes_f16, uint16_t *out_f16, in
 int pca_debug_bev_stamps(unsigned long long *out)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg_stamps), sizeof(unsigned long long) * 8192);
+}
+
+// diagnostic, read only: {points per thread parked in LDS, bytes of dynamic LDS} of level 1 as the process's last
+// pca_bev_generate_chain launched it (process-wide, like the stamps above: tests that read it make one raster at a time)
+int pca_debug_bev_lds(int out[2])
+{
+    if (!out) return -1;
+    out[0] = g_last_lds[0]; out[1] = g_last_lds[1];
+    return 0;
 }
 
 // diagnostic, read only: level 1's grid as the last pca_bev_generate_chain of the context launched it

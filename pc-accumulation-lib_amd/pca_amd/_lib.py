@@ -30,7 +30,7 @@ EXPORTS = ('pca_version', 'pca_ctx_create', 'pca_ctx_destroy', 'pca_last_error',
            'pca_host_track_step', 'pca_host_track_trigger', 'pca_host_stage_h2d', 'pca_host_d2h_async', 'pca_host_d2h_wait',
            'pca_deflate_workspace_bytes', 'pca_deflate_chunks', 'pca_deflate_chunks_dyn', 'pca_host_crc32_combine', 'pca_host_gzip_assemble',
            'pca_preview_stream_bytes', 'pca_preview_workspace_bytes', 'pca_preview_sheets', 'pca_adler32_chunks', 'pca_host_adler32_combine', 'pca_host_png_assemble',
-           'pca_kitti_integrate', 'pca_kitti_generate_bev', 'pca_k1_defer', 'pca_k1_flush', 'pca_host_camera_cone', 'pca_host_view_hull', 'pca_bev_bin_range', 'pca_bev_view_hint', 'pca_kitti_integrate_v', 'pca_kitti_generate_bev_v', 'pca_f32_box_decode', 'pca_debug_bev_level1', 'pca_debug_icp_layout',
+           'pca_kitti_integrate', 'pca_kitti_generate_bev', 'pca_k1_defer', 'pca_k1_flush', 'pca_host_camera_cone', 'pca_host_view_hull', 'pca_bev_bin_range', 'pca_bev_view_hint', 'pca_kitti_integrate_v', 'pca_kitti_generate_bev_v', 'pca_f32_box_decode', 'pca_debug_bev_level1', 'pca_debug_bev_lds', 'pca_debug_icp_layout',
            'pca_profile_enable', 'pca_profile_read')
 
 KERNEL_IDS = ('kitti_project_sample_filter', 'nusc_sample_filter_transform', 'nusc_project_cams', 'retransform',
@@ -358,6 +358,7 @@ def load():
     lib.pca_f32_box_decode.argtypes = [vp, i32, vp]
     lib.pca_f32_box_decode.restype = None
     lib.pca_debug_bev_level1.argtypes = [vp, vp]
+    lib.pca_debug_bev_lds.argtypes = [vp]
     lib.pca_debug_icp_layout.argtypes = [i32, i32, C.POINTER(C.c_int64)]
     lib.pca_kitti_integrate_v.argtypes = [vp, vp]
     lib.pca_kitti_generate_bev_v.argtypes = [vp, vp]
